@@ -18,7 +18,15 @@ N > 1 GPUs (torchrun, one process per GPU): every rank proves its own independen
 rank count: under a launcher WORLD_SIZE must equal it (else exit 2); started bare with N > 1 the
 script launches its own N ranks (torch.distributed.run, 127.0.0.1) as a child process.
 
-Extra fields in the JSON line:
+A plain run does only what the headline needs: it sets up, warms up the device-resident path, times
+`--steps` proofs, and prints the line (metric, value, unit, ms_per_step, config, ...). `--dump-outputs
+DIR` writes, after the timed steps, the last timed proof of every in-flight context as
+DIR/commitments_ctx<i>.npy (6 x 16) and DIR/evaluations_ctx<i>.npy (3 x 8 for the default workload):
+float64 arrays of the proof's 32-bit little-endian words, exact (N > 1: prefixed rank<r>_). The inputs
+are seeded, so two builds run with the same arguments can be compared output for output. Every other
+leg below runs only with `--full`, `latency_ms_single_proof` among them.
+
+Extra fields in the JSON line of a `--full` run:
   proof_verified : one proof of the timed workload checked with the native verifier (pairing)
   host_buffer_inflight : the same steps, in flight the same way, through the drop-in boundary: kgs_prove
               on pageable host F/T with the Montgomery write-back into caller-owned host buffers
@@ -306,6 +314,12 @@ def main():
                          "print {n_gpus, ranks_joined} from rank 0 and exit (no GPU touched; CPU test of the launch)")
     ap.add_argument("--inflight", type=int, default=4,
                     help="independent proofs in flight per GPU (one context + HIP stream + host thread each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: proof checks, single-proof latency, the host-buffer "
+                         "and JavaScript legs, MSM phases / roofline, CPU baseline and the extra configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed proof of every in-flight context to "
+                         "DIR/<name>.npy (float64 arrays holding the proof's 32-bit little-endian words)")
     args = ap.parse_args()
     # --gpus N is the number of ranks. Under a launcher (torchrun / torch.distributed.run) WORLD_SIZE
     # must agree with it; started bare with N > 1, bench.py launches its N ranks itself (one process
@@ -376,18 +390,23 @@ def main():
             keep += [tf, tt]
             d_f.append(tf.data_ptr())
             d_t.append(tt.data_ptr())
-            h_f.append(f.tobytes())
-            h_t.append(t.tobytes())
-        wb = ([bytearray(32 * n) for _ in range(args.npols)], [bytearray(32 * n) for _ in range(args.npols)])
+            if args.full:  # only the host-buffer legs read these
+                h_f.append(f.tobytes())
+                h_t.append(t.tobytes())
         bufs.append((d_f, d_t))
-        hbufs.append((h_f, h_t, wb))
+        if args.full:
+            wb = ([bytearray(32 * n) for _ in range(args.npols)], [bytearray(32 * n) for _ in range(args.npols)])
+            hbufs.append((h_f, h_t, wb))
     torch.cuda.synchronize()
+
+    # what the caller of the timed path receives: the last (commitments, evaluations) of each context
+    last_proof = [None] * len(ctxs)
 
     def run_dev(ci, count):
         c = ctxs[ci]
         d_f, d_t = bufs[ci]
         for _ in range(count):
-            c.prove_device(kind, nbits, d_f, d_t)
+            last_proof[ci] = c.prove_device(kind, nbits, d_f, d_t)
 
     def run_host(ci, count):
         c = ctxs[ci]
@@ -417,38 +436,40 @@ def main():
         c.set_msm_lanes(1 if len(ctxs) > 1 else 2)
     log("warm-up")
     steps(max(args.warmup, len(ctxs)), run_dev)
-    steps(max(args.warmup, len(ctxs)), run_host)
-    # single-proof latency (one proof at a time on one context), outside the timed region: median and
-    # spread of LAT_SAMPLES proofs, device-resident and through the host-buffer boundary
     LAT_SAMPLES = 7
-    ctx.set_msm_lanes(2)
-    run_dev(0, 1)
-    t_lat = []
-    for _ in range(LAT_SAMPLES):
-        t1 = time.perf_counter()
+    if args.full:
+        steps(max(args.warmup, len(ctxs)), run_host)
+        # single-proof latency (one proof at a time on one context), outside the timed region: median and
+        # spread of LAT_SAMPLES proofs, device-resident and through the host-buffer boundary
+        ctx.set_msm_lanes(2)
         run_dev(0, 1)
-        t_lat.append(time.perf_counter() - t1)
-    rounds = ctx.last_timing()
-    run_host(0, 1)
-    t_hlat, h_timing = [], []
-    for _ in range(LAT_SAMPLES):
-        t1 = time.perf_counter()
+        t_lat = []
+        for _ in range(LAT_SAMPLES):
+            t1 = time.perf_counter()
+            run_dev(0, 1)
+            t_lat.append(time.perf_counter() - t1)
+        rounds = ctx.last_timing()
         run_host(0, 1)
-        t_hlat.append(time.perf_counter() - t1)
-        h_timing.append(ctx.last_timing())
-    latency = stats_ms(t_lat)
-    latency_ms = latency["median"]
-    # the proofs the bench times are real: one device-resident proof checked with the native verifier
-    # (pairing), and the host-buffer path must give the identical proof and write back F's Montgomery form
-    d_f0, d_t0 = bufs[0]
-    coms0, evs0 = ctx.prove_device(kind, nbits, d_f0, d_t0)
-    cn0, en0 = K.proof_names(kind, args.npols, False)
-    vf = K.grandsum_verifier if kind == K.GRANDSUM else K.grandproduct_verifier
-    proof_verified = vf(ptau, {"commitments": dict(zip(cn0, coms0)), "evaluations": dict(zip(en0, evs0))}, nbits)
-    h_f0, h_t0, _ = hbufs[0]
-    hcoms, hevs, hmf, _ = ctx.prove(kind, nbits, h_f0, h_t0)
-    host_identical = hcoms == coms0 and hevs == evs0 and bytes(hmf[0][:32 * 64]) == ctx.fr_to_mont(h_f0[0][:32 * 64])
-    ctx.set_msm_lanes(1 if len(ctxs) > 1 else 2)
+        t_hlat, h_timing = [], []
+        for _ in range(LAT_SAMPLES):
+            t1 = time.perf_counter()
+            run_host(0, 1)
+            t_hlat.append(time.perf_counter() - t1)
+            h_timing.append(ctx.last_timing())
+        latency = stats_ms(t_lat)
+        latency_ms = latency["median"]
+        # the proofs the bench times are real: one device-resident proof checked with the native verifier
+        # (pairing), and the host-buffer path must give the identical proof and write back F's Montgomery form
+        d_f0, d_t0 = bufs[0]
+        coms0, evs0 = ctx.prove_device(kind, nbits, d_f0, d_t0)
+        cn0, en0 = K.proof_names(kind, args.npols, False)
+        vf = K.grandsum_verifier if kind == K.GRANDSUM else K.grandproduct_verifier
+        proof_verified = vf(ptau, {"commitments": dict(zip(cn0, coms0)), "evaluations": dict(zip(en0, evs0))}, nbits)
+        h_f0, h_t0, _ = hbufs[0]
+        hcoms, hevs, hmf, _ = ctx.prove(kind, nbits, h_f0, h_t0)
+        host_identical = (hcoms == coms0 and hevs == evs0
+                          and bytes(hmf[0][:32 * 64]) == ctx.fr_to_mont(h_f0[0][:32 * 64]))
+        ctx.set_msm_lanes(1 if len(ctxs) > 1 else 2)
 
     def timed(fn, label):
         if dist:
@@ -469,32 +490,43 @@ def main():
     total_proofs = args.steps * world
     value = total_proofs / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
-    log(f"timed: {value:.2f} proofs/s device-resident; host-buffer in flight")
-    # the host-buffer path in flight: three regions of the same K steps, interleaved with two more
-    # device-resident ones, so the ratio compares medians of neighbouring runs (a single pair of runs
-    # spread 0.95-0.99 on one box, profiles/r06/host_inflight_modes.txt); `value` stays the first region
-    el_hosts, el_devs = [], [elapsed]
-    for i in range(3):
-        el_hosts.append(timed(run_host, "kgs_bench_host_region"))
-        if i < 2:
-            el_devs.append(timed(run_dev, "kgs_bench_timed_region_extra"))
-    el_host = float(np.median(el_hosts))
-    host_inflight = {
-        "proofs_per_s": round(total_proofs / el_host, 4), "ms_per_step": round(1000.0 * el_host / args.steps, 3),
-        "vs_device_resident": round(float(np.median(el_devs)) / el_host, 4),
-        "samples_proofs_per_s": [round(total_proofs / x, 3) for x in el_hosts],
-        "device_samples_proofs_per_s": [round(total_proofs / x, 3) for x in el_devs],
-        "proof_identical_to_device_path": host_identical,
-        "note": (f"kgs_prove on pageable host F/T, {len(ctxs)} contexts in flight, Montgomery forms written back into "
-                 "caller-owned host buffers (prover.js:147-148): PCIe-inclusive, K steps per region like `value`; "
-                 "median of 3 regions, ratio against the median of 3 device-resident regions (the first is `value`) "
-                 "run interleaved")}
+    log(f"timed: {value:.2f} proofs/s device-resident")
+    if args.dump_outputs:
+        # each context proves the same multiset in every step, so its last proof is the step's output;
+        # a proof is a few hundred bytes, its 32-bit little-endian words are exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        pre = f"rank{rank}_" if world > 1 else ""
+        for ci, (coms, evs) in enumerate(last_proof):
+            for name, parts in (("commitments", coms), ("evaluations", evs)):
+                words = np.frombuffer(b"".join(parts), dtype="<u4").reshape(len(parts), -1)
+                np.save(os.path.join(args.dump_outputs, f"{pre}{name}_ctx{ci}.npy"), words.astype(np.float64))
+    host_inflight = None
+    if args.full:
+        # the host-buffer path in flight: three regions of the same K steps, interleaved with two more
+        # device-resident ones, so the ratio compares medians of neighbouring runs (a single pair of runs
+        # spread 0.95-0.99 on one box, profiles/r06/host_inflight_modes.txt); `value` stays the first region
+        el_hosts, el_devs = [], [elapsed]
+        for i in range(3):
+            el_hosts.append(timed(run_host, "kgs_bench_host_region"))
+            if i < 2:
+                el_devs.append(timed(run_dev, "kgs_bench_timed_region_extra"))
+        el_host = float(np.median(el_hosts))
+        host_inflight = {
+            "proofs_per_s": round(total_proofs / el_host, 4), "ms_per_step": round(1000.0 * el_host / args.steps, 3),
+            "vs_device_resident": round(float(np.median(el_devs)) / el_host, 4),
+            "samples_proofs_per_s": [round(total_proofs / x, 3) for x in el_hosts],
+            "device_samples_proofs_per_s": [round(total_proofs / x, 3) for x in el_devs],
+            "proof_identical_to_device_path": host_identical,
+            "note": (f"kgs_prove on pageable host F/T, {len(ctxs)} contexts in flight, Montgomery forms written back "
+                     "into caller-owned host buffers (prover.js:147-148): PCIe-inclusive, K steps per region like "
+                     "`value`; median of 3 regions, ratio against the median of 3 device-resident regions (the first "
+                     "is `value`) run interleaved")}
+        log(f"host-buffer in flight: {host_inflight['proofs_per_s']:.2f} proofs/s; JS leg")
 
     # ---------------- host-buffer boundary latency (what the JS / Python drop-in modules call): kgs_prove
     # on pageable host buffers, including the H2D copy of F/T and the D2H Montgomery write-back
-    log(f"host-buffer in flight: {host_inflight['proofs_per_s']:.2f} proofs/s; JS leg")
     host_leg = None
-    if rank == 0 and args.host_leg:
+    if args.full and rank == 0 and args.host_leg:
         hl = stats_ms(t_hlat)
         best = min(range(len(t_hlat)), key=lambda i: t_hlat[i])
         host_leg = {"ms_per_proof": hl["median"], "latency_ms": hl, "proofs_per_s": round(1000.0 / hl["median"], 3),
@@ -535,7 +567,7 @@ def main():
 
     msm = roofline = hbm_view = cpu = None
     extra_cfg = {}
-    if rank == 0:
+    if args.full and rank == 0:
         log("MSM leg")
         # ---------------- MSM leg: live HIP-event timing of the phases at N = n
         sc = torch.from_numpy(synth_evals(n, 777)[0].reshape(-1).copy()).to(f"cuda:{local}")
@@ -673,6 +705,16 @@ def main():
                    "nbits": nbits, "npols": args.npols, "selectors": False, "parallelism": f"replicas x{world}", "inflight_per_gpu": args.inflight,
                    "srs_power": power, "srs_points_resident": npts, "srs_gen_s": round(t_gen, 2),
                    "srs_load_s": round(t_load, 2)},
+    }
+    if not args.full:
+        # a plain run ends with its headline: set up, warm up, time the steps, dump, print
+        if rank == 0:
+            print(json.dumps(out), file=json_out, flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    out.update({
         "proof_verified": proof_verified,
         "host_buffer_inflight": host_inflight,
         "host_buffer_boundary": host_leg,
@@ -684,7 +726,7 @@ def main():
         "hbm_view": hbm_view,
         "extra_configs": extra_cfg,
         "cpu_baseline": cpu,
-    }
+    })
 
     # The extra legs run last, under a watchdog: at N > 1 they exercise the RCCL transport of the
     # distributed prover, and a rank that hangs there must not cost the headline line. On expiry rank

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     reps, libs = int(sys.argv[1]), sys.argv[2:]
-    args = ["--no-cpu-baseline", "--no-extra-legs", "--no-host-leg", "--steps", "64", "--msm-reps", "10"]
+    args = ["--full", "--no-cpu-baseline", "--no-extra-legs", "--no-host-leg", "--steps", "64", "--msm-reps", "10"]
     for rep in range(1, reps + 1):
         for lib in libs:
             env = dict(os.environ, KGS_LIB=os.path.abspath(lib))

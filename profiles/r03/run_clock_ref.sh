@@ -13,5 +13,5 @@ timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT SQ_INSTS_VALU SQ_
 python3 $R/profiles/summarize_clock.py $OUT/pmc/run_counter_collection.csv 50 > $OUT/clock_madd29.txt
 cat $OUT/clock_madd29.txt
 cd $R
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cat $OUT/bench_default.json

@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 $OUT/smoke.log
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/bench_prof -o run -- python3 $R/bench.py > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/bench_prof -o run -- python3 $R/bench.py --full > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cat $OUT/bench_under_rocprof.json
 python3 $R/profiles/summarize_window.py $OUT/bench_prof/run 5 kgs_bench_msm_leg > $OUT/bench_windows.txt
 python3 $R/profiles/summarize_window.py $OUT/bench_prof/run 32 >> $OUT/bench_windows.txt
@@ -26,5 +26,5 @@ timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT SQ_INSTS_VALU SQ_
 python3 $R/profiles/summarize_clock.py $OUT/pmc_clock/run_counter_collection.csv > $OUT/clock_valu.txt
 cat $OUT/clock_valu.txt
 cd $R
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cat $OUT/bench_default.json

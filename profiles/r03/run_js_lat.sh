@@ -11,5 +11,5 @@ for i in 1 2; do
   KGS_JS_CONTEXTS=8 KGS_DEVICES=0 timeout -k 10 300 node kzg-grandsums-study_amd/js/test/time_prove.js /tmp/kgs_bench_p20.ptau 20 5 16 > $OUT/js_$i.json
   cat $OUT/js_$i.json
 done
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['latency_ms_single_proof'], json.dumps(d['host_buffer_boundary'])[:700])"

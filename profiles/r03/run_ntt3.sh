@@ -26,5 +26,5 @@ cd /tmp && export TMPDIR=/tmp
 timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d $R/$OUT/kt21 -o run -- python3 $R/profiles/ntt_ab.py 21 20
 python3 $R/profiles/summarize_trace.py $R/$OUT/kt21/run_kernel_trace.csv $R/$OUT/kt21.csv
 cd $R
-timeout -k 10 300 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json

@@ -6,7 +6,7 @@ set -e
 cd "$(dirname "$0")/../.."
 OUT=gpurun_out/r03d
 mkdir -p $OUT
-KGS_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --c4-nbits 20 --sv-nbits 18 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
+KGS_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --full --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --c4-nbits 20 --sv-nbits 18 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
 echo "rc=$?"
 cat $OUT/bench_n2_gloo.json
 P=/tmp/kgs_bench_p20.ptau

@@ -11,7 +11,7 @@ timeout -k 10 200 python3 profiles/boundary_probe.py 20 5 > $OUT/boundary.txt 2>
 grep -v amdgpu.ids $OUT/boundary.txt
 KGS_JS_CONTEXTS=8 KGS_DEVICES=0 timeout -k 10 300 node kzg-grandsums-study_amd/js/test/time_prove.js /tmp/kgs_bench_p20.ptau 20 5 16 > $OUT/js.json
 cat $OUT/js.json
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 180 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -o run -- python3 $R/profiles/prove_loop.py 20 1 > $OUT/prove_loop.txt 2>&1

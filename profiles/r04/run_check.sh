@@ -15,8 +15,8 @@ python3 $R/profiles/summarize_valu.py $OUT/pmc_valu > $OUT/valu_share.txt
 head -3 $OUT/valu_share.txt
 cd $R
 for k in 4 5 6 4; do
-  timeout -k 10 200 python3 bench.py --inflight $k --no-cpu-baseline --no-extra-legs --no-host-leg --steps 64 --msm-reps 5 > $OUT/inflight_$k.json 2>> $OUT/inflight.err
+  timeout -k 10 200 python3 bench.py --full --inflight $k --no-cpu-baseline --no-extra-legs --no-host-leg --steps 64 --msm-reps 5 > $OUT/inflight_$k.json 2>> $OUT/inflight.err
   echo "inflight $k: $(python3 -c "import json; d=json.load(open('$OUT/inflight_$k.json')); print(d['value'], d['latency_ms_single_proof'])")"
 done
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python3 -c "import json; d=json.load(open('$OUT/bench_default.json')); print('default', d['value'], d['latency_ms_single_proof'], d['roofline']['frac'], d['host_buffer_boundary']['javascript_module'].get('ms_per_proof'), d['host_buffer_boundary']['javascript_module'].get('concurrent_proofs_per_s'))"

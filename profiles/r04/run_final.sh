@@ -14,7 +14,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 $OUT/smoke.log
 fi
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/bench_prof -o run -- python3 $R/bench.py > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+timeout -k 10 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $OUT/bench_prof -o run -- python3 $R/bench.py --full > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 cat $OUT/bench_under_rocprof.json
 python3 $R/profiles/summarize_window.py $OUT/bench_prof/run 5 kgs_bench_msm_leg > $OUT/bench_windows.txt
 python3 $R/profiles/summarize_window.py $OUT/bench_prof/run 32 >> $OUT/bench_windows.txt
@@ -26,7 +26,7 @@ timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT SQ_INSTS_VALU SQ_
 python3 $R/profiles/summarize_clock.py $OUT/pmc_clock/run_counter_collection.csv > $OUT/clock_valu.txt
 cat $OUT/clock_valu.txt
 cd $R
-timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cat $OUT/bench_default.json
 # per-kernel VALU share of one proof (VERDICT r3 Next #3: NTT share)
 cd /tmp
@@ -35,5 +35,5 @@ python3 $R/profiles/summarize_valu.py $OUT/pmc_valu > $OUT/valu_share_per_proof_
 head -12 $OUT/valu_share_per_proof_2p20.txt
 cd $R
 # the N = 2 path rehearsed on the one-GPU box (gloo host collectives; VERDICT r3 Next #7)
-KGS_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --c4-nbits 20 --sv-nbits 18 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
+KGS_BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --full --gpus 2 --steps 8 --warmup 2 --no-cpu-baseline --no-host-leg --c4-nbits 20 --sv-nbits 18 > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err
 cat $OUT/bench_n2_gloo.json

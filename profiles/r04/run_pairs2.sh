@@ -19,7 +19,7 @@ cat $OUT/msm_phases.txt
 ARGS="--no-cpu-baseline --no-extra-legs --no-host-leg --steps 64 --msm-reps 10"
 for rep in 1 2 3; do
   for P in 0 1; do
-    KGS_ACC_PAIRS=$P timeout -k 10 180 python3 bench.py $ARGS > $OUT/b.json 2> $OUT/b.err
+    KGS_ACC_PAIRS=$P timeout -k 10 180 python3 bench.py --full $ARGS > $OUT/b.json 2> $OUT/b.err
     python3 -c "import json;d=json.load(open('$OUT/b.json'));print('pairs=$P rep $rep:', d['value'], 'lat', d['latency_ms_single_proof'], 'acc', d['msm']['phase_ms'])" >> $OUT/bench_ab.txt
   done
 done

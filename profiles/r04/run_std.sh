@@ -15,6 +15,6 @@ python3 $R/profiles/summarize_valu.py $OUT/pmc_valu > $OUT/valu_share.txt
 head -1 $OUT/valu_share.txt; grep sort_ $OUT/valu_share.txt
 cd $R
 for k in 1 2; do
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-extra-legs --no-host-leg --steps 64 --msm-reps 5 > $OUT/bench_$k.json 2>> $OUT/bench.err
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-extra-legs --no-host-leg --steps 64 --msm-reps 5 > $OUT/bench_$k.json 2>> $OUT/bench.err
   echo "bench $k: $(python3 -c "import json; d=json.load(open('$OUT/bench_$k.json')); print(d['value'], d['latency_ms_single_proof'], d['msm']['phase_ms'])")"
 done

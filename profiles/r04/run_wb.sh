@@ -16,5 +16,5 @@ for rep in 1 2; do
   done
 done
 grep -E "==|host  " $OUT/boundary_ab.txt | head -40
-timeout -k 10 300 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 python3 -c "import json;d=json.load(open('$OUT/bench_default.json'));print(d['value'], d['latency_ms_single_proof'], d['host_buffer_boundary']['ms_per_proof'], d['host_buffer_boundary']['javascript_module']['ms_per_proof'], d['host_buffer_boundary']['javascript_module']['concurrent_proofs_per_s'])"

@@ -9,7 +9,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 900 --timeout
 tail -20 $O/gpu_tests.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; cat $O/smoke.log; exit 1; }
 cat $O/smoke.log
-timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.log || { echo "bench rc=$?"; tail -20 $O/bench_default.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.log || { echo "bench rc=$?"; tail -20 $O/bench_default.log; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/bench_default.json'))
 h=d['host_buffer_boundary']; j=h.get('javascript_module',{})

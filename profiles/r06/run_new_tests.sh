@@ -18,5 +18,5 @@ tail -15 $O/new_tests.log
 timeout -k 10 120 ./profiles/ubench/host_copy_bw > $O/host_copy_bw.txt 2>&1 || { echo "ubench failed"; exit 1; }
 cat $O/host_copy_bw.txt
 lscpu > $O/lscpu.txt 2>&1; cat /sys/fs/cgroup/cpu.max >> $O/lscpu.txt 2>/dev/null
-timeout -k 10 600 python -u bench.py > $O/bench_default.json 2> $O/bench_default.log || { echo "bench rc=$?"; tail -20 $O/bench_default.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.log || { echo "bench rc=$?"; tail -20 $O/bench_default.log; exit 1; }
 cat $O/bench_default.json

@@ -17,7 +17,7 @@ for cc in 20 18; do
 done
 for rep in 1 2; do
   for cc in 17 20; do
-    KGS_MSM_C=$cc timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-extra-legs --no-host-leg > $O/bench_c${cc}_$rep.json 2> $O/bench_c${cc}_$rep.log || { echo "bench c=$cc failed"; tail -20 $O/bench_c${cc}_$rep.log; exit 1; }
+    KGS_MSM_C=$cc timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-extra-legs --no-host-leg > $O/bench_c${cc}_$rep.json 2> $O/bench_c${cc}_$rep.log || { echo "bench c=$cc failed"; tail -20 $O/bench_c${cc}_$rep.log; exit 1; }
     python3 -c "import json;d=json.load(open('$O/bench_c${cc}_$rep.json'));m=d['msm'];print('c=$cc rep $rep', d['value'], 'proofs/s; msm', m['ms'], m['phase_ms'], 'latency', d['latency_ms_single_proof'])"
   done
 done
