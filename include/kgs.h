@@ -41,6 +41,8 @@ extern "C" {
 #define KGS_E_COMM (-8)            /* the shard all-gather callback reported a failure */
 #define KGS_E_RANGE (-9)           /* reference-quirks mode only: "offset is out of bounds", the V8 RangeError the
                                       reference's divZh throws for a zero quotient (polynomial.js:857,884) */
+#define KGS_E_NOT_IN_TABLE (-10)   /* "Row <i> of F is not in the table." (kgs_lookup_multiplicities: the lowest
+                                      selected row of F that equals no row of the table) */
 
 #define KGS_GRANDSUM 0
 #define KGS_GRANDPRODUCT 1
@@ -284,6 +286,32 @@ int kgs_poly_eval(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, const 
 /* Polynomial.divByXSubValue (polynomial.js:814-851); out has `len` coefficients */
 int kgs_poly_div_x_sub(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, const uint8_t z_mont[32],
                        uint8_t* out_mont);
+/* Multiplicities of a lookup (the sel_t of a KGS_LOOKUP proof) from the witness and the table: a hash
+ * join on the GPU. mul_t[j] = number of rows i of F with sel_f[i] == one that equal row j of T,
+ * as a 32 B Montgomery element. No SRS is needed.
+ *   npols     k in 1 .. 32; a row is the k-tuple (col_0[i], .., col_{k-1}[i])
+ *   n         rows of F and of T, any value in 1 .. 2^28 (not only powers of two)
+ *   evals_f/t k host pointers, n x 32 B STANDARD-form evaluations each, as kgs_prove takes them (read
+ *             only). Rows are equal when all k components are equal as elements of Fr: a stored value
+ *             v >= r counts as v mod r.
+ *   sel_f     n x 32 B MONTGOMERY selector (zero or one per row), or NULL: every row is selected
+ * A table row that occurs several times receives ALL of its multiplicity at its FIRST occurrence (the
+ * lowest index); its later occurrences get zero. Any split over the occurrences proves; this one is
+ * fixed so that the output is the same bytes on every run.
+ * Failures (the output's contents are then unspecified):
+ *   KGS_E_ARG           "selF is not binary at row <i>." — the lowest row whose selector is neither
+ *                       zero nor one (reported before a missing row); bad npols / n / NULL; a context
+ *                       attached to a rank group (kgs_ctx_set_group: not supported)
+ *   KGS_E_NOT_IN_TABLE  "Row <i> of F is not in the table." — the lowest selected row without a match
+ * Like the provers, the call returns with nothing pending on the context's streams, on its error
+ * paths too (kgs_ctx_idle). */
+int kgs_lookup_multiplicities(kgs_ctx_t* ctx, int npols, uint64_t n, const uint8_t* const* evals_f,
+                              const uint8_t* const* evals_t, const uint8_t* sel_f, uint8_t* mul_t_mont);
+/* Same with device pointers in and out (on ctx's device): the n x 32 B output is what
+ * kgs_prove_device(KGS_LOOKUP, ..) takes as d_sel_t, so a device-resident witness and table never
+ * leave the GPU between the two calls. */
+int kgs_lookup_multiplicities_device(kgs_ctx_t* ctx, int npols, uint64_t n, const void* const* d_evals_f,
+                                     const void* const* d_evals_t, const void* d_sel_f, void* d_mul_t_mont);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 

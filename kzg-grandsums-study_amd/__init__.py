@@ -97,6 +97,9 @@ def lib():
                                       ctypes.c_uint64, c_u8p]
         L.kgs_poly_eval.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, c_u8p]
         L.kgs_poly_div_x_sub.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, c_u8p]
+        L.kgs_lookup_multiplicities.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, PP, PP, c_u8p, c_u8p]
+        L.kgs_lookup_multiplicities_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, PP, PP,
+                                                       ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_keccak256.argtypes = [c_u8p, ctypes.c_uint64, c_u8p]
         L.kgs_bench_msm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                     ctypes.POINTER(ctypes.c_double)]
@@ -516,6 +519,46 @@ class Context:
         _check(lib().kgs_poly_div_x_sub(self._h, _buf(coef_mont), len(coef_mont) // 32, _buf(z_mont), out))
         return out.raw
 
+    def lookup_multiplicities(self, evals_f, evals_t, sel_f=None):
+        """Multiplicities of the table rows of a lookup (kgs_lookup_multiplicities): evals_f / evals_t are
+        lists of k standard-form buffers of n 32-byte elements (any n >= 1), sel_f a Montgomery selector
+        or None (every row selected). Returns n Montgomery elements as a bytearray: the evalsMulT of
+        lookup_prover. A repeated table row gets all of its count at its first occurrence. Inputs are
+        read in place and left as they are."""
+        k = len(evals_f)
+        if k == 0 or len(evals_t) != k:
+            raise ValueError("evals_f and evals_t must be two lists of the same, nonzero number of columns")
+        nbytes = len(evals_f[0])
+        bufs = list(evals_f) + list(evals_t) + ([sel_f] if sel_f is not None else [])
+        if nbytes == 0 or nbytes % 32 or any(len(x) != nbytes for x in bufs):
+            raise ValueError("every buffer must hold the same number (>= 1) of 32-byte elements")
+        keep = []
+        PF = (ctypes.c_void_p * k)()
+        PT = (ctypes.c_void_p * k)()
+        for i in range(k):
+            (pf, kf), (pt, kt) = _ptr(evals_f[i]), _ptr(evals_t[i])
+            keep += [kf, kt]
+            PF[i], PT[i] = pf, pt
+        sf = None
+        if sel_f is not None:
+            sf, ksf = _ptr(sel_f)
+            keep.append(ksf)
+        out = _uninit_bytearray(nbytes)
+        po, ko = _ptr(out)
+        keep.append(ko)
+        _check(lib().kgs_lookup_multiplicities(self._h, k, nbytes // 32, PF, PT, sf, po))
+        return out
+
+    def lookup_multiplicities_device(self, d_f, d_t, d_sf, d_out, n):
+        """Device-resident twin (kgs_lookup_multiplicities_device): d_f / d_t are lists of device pointers
+        (ints) to n standard-form elements, d_sf a device pointer to the Montgomery selector or None,
+        d_out a device pointer to n x 32 writable bytes — afterwards the d_st of
+        prove_device(LOOKUP, ..)."""
+        k = len(d_f)
+        PF = (ctypes.c_void_p * k)(*d_f)
+        PT = (ctypes.c_void_p * k)(*d_t)
+        _check(lib().kgs_lookup_multiplicities_device(self._h, k, n, PF, PT, d_sf, d_out))
+
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
         sent, host all-gather count / wall ms / bytes sent; zeros after a single-GPU proof."""
@@ -891,6 +934,54 @@ def lookup_prover(pTauFilename, evalsFs, evalsTs, evalsSelF=None, evalsMulT=None
         return _prover(LOOKUP, pTauFilename, evalsFs, evalsTs, evalsSelF, evalsMulT, device)
     except KgsError as e:
         raise _semantic(e) from e
+
+
+def _lookup_lengths(evalsFs, evalsTs, evalsSelF):
+    """_prover's list / length checks (same messages) for the calls that take no multiplicities."""
+    if not isinstance(evalsFs, (list, tuple)):
+        evalsFs = [evalsFs]
+    if not isinstance(evalsTs, (list, tuple)):
+        evalsTs = [evalsTs]
+    if len(evalsFs) != len(evalsTs):
+        raise ValueError("The lengths of the two vector multisets must be the same.")
+    npols = len(evalsFs)
+    if npols == 0:
+        raise ValueError("The number of multisets must be greater than 0.")
+    for i in range(npols):
+        if evalsFs[i].length() != evalsTs[i].length():
+            raise ValueError(f"The {i}-th multiset buffers must have the same length.")
+        elif evalsFs[i].length() != evalsFs[0].length():
+            raise ValueError("The multiset buffers must all have the same length.")
+    if evalsSelF is not None and evalsSelF.length() != evalsFs[0].length():
+        raise ValueError("The selection buffers must have the same length as the multiset buffers.")
+    return evalsFs, evalsTs
+
+
+def lookup_multiplicities(evalsFs, evalsTs, evalsSelF=None, device=0):
+    """The evalsMulT of lookup_prover, computed on the GPU (include/kgs.h kgs_lookup_multiplicities): for
+    every row of the table evalsTs, how many rows of evalsFs selected by evalsSelF (Montgomery zero /
+    one; all rows if None) equal it. evalsFs / evalsTs are standard-form Evaluations (one, or a list of
+    k columns) and are not modified. A table row that occurs several times gets all of its count at its
+    first occurrence. Raises ValueError "Row <i> of F is not in the table." for the lowest selected row
+    without a match."""
+    evalsFs, evalsTs = _lookup_lengths(evalsFs, evalsTs, evalsSelF)
+    if evalsFs[0].length() == 0:
+        raise ValueError("The multiset buffers must not be empty.")
+    try:
+        m = _context(device).lookup_multiplicities([e.eval for e in evalsFs], [e.eval for e in evalsTs],
+                                                   evalsSelF.eval if evalsSelF is not None else None)
+    except KgsError as e:
+        raise _semantic(e) from e
+    out = Evaluations(b"")
+    out.eval = m
+    return out
+
+
+def lookup_prover_from_table(pTauFilename, evalsFs, evalsTs, evalsSelF=None, device=0):
+    """lookup_prover with the multiplicities computed from the table (lookup_multiplicities): the caller
+    passes the witness, the table and, optionally, the selector of the witness rows."""
+    evalsMulT = lookup_multiplicities(evalsFs, evalsTs, evalsSelF, device)
+    return lookup_prover(pTauFilename, evalsFs, evalsTs, evalsSelF, evalsMulT, device)
 
 
 def lookup_verifier(pTauFilename, proof, nBits):

@@ -1,4 +1,4 @@
-// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip). All pointers are device
+// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip). All pointers are device
 // pointers to 32 B Montgomery Fr elements (uint32_t[8]) or 64 B affine / 128 B XYZZ G1 points,
 // unless stated otherwise. Launches are asynchronous on `st`.
 #pragma once
@@ -136,6 +136,21 @@ void launch_quotient_e(hipStream_t st, bool prod, bool sel, uint32_t* q, const u
 void launch_nxm1_e(hipStream_t st, uint32_t* out, const uint32_t* tw, int lcs, const uint32_t* gp, const uint32_t* np,
                    int W, int r);
 void launch_div_fix(hipStream_t st, uint32_t* q, const uint32_t* pz, const uint32_t* c, uint64_t Lb);
+
+// lookup.hip
+// k columns of 32 B STANDARD-form elements (any 256-bit value; rows compare as elements of Fr)
+struct LookupCols {
+  int k;
+  const uint32_t* col[EB_MAX];
+};
+// out[j] (Montgomery) = number of rows i < n of F with sel_f[i] == one (nullptr: every row) that equal
+// row j of T, a repeated table row's whole count on its lowest index. table: `capacity` (a power of two
+// >= 2n) words preset to 0xFFFFFFFF; count: n words preset to 0; flags: two words preset to
+// 0xFFFFFFFF that receive the lowest row of F missing from T and the lowest row whose selector is
+// neither zero nor Montgomery one.
+void launch_lookup_multiplicities(hipStream_t st, uint32_t* out, uint32_t* table, uint64_t capacity, uint32_t* count,
+                                  uint32_t* flags, const LookupCols& F, const LookupCols& T, const uint32_t* sel_f,
+                                  uint64_t n);
 
 // msm.hip
 void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int W, uint32_t* tmp_xyzz,

@@ -2223,6 +2223,92 @@ int kgs_poly_div_x_sub(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, c
   API_END
 }
 
+}  // extern "C"
+
+// Multiplicities of a lookup table (kgs.h; kernels in lookup.hip) on the context's main stream: device
+// inputs, device output, and the output's copy to `host_out` when that is given. Returns once the
+// stream is drained; the two error rows come back through the flags.
+static void lookup_multiplicities_impl(kgs_ctx& c, uint64_t n, const LookupCols& F, const LookupCols& T,
+                                       const uint32_t* sel_f, uint32_t* out, uint8_t* host_out) {
+  uint64_t cap = 2;
+  while (cap < 2 * n) cap <<= 1;
+  uint32_t* table = c.buf("lk_table", 4 * cap);
+  uint32_t* count = c.buf("lk_count", 4 * n);
+  uint32_t* flags = c.buf("flags", 64);
+  HC(hipMemsetAsync(table, 0xFF, 4 * cap, c.st));
+  HC(hipMemsetAsync(count, 0, 4 * n, c.st));
+  HC(hipMemsetAsync(flags, 0xFF, 64, c.st));
+  launch_lookup_multiplicities(c.st, out, table, cap, count, flags, F, T, sel_f, n);
+  check_launch();
+  uint32_t* hf = (uint32_t*)c.pin(64);
+  if (host_out) HC(hipMemcpyAsync(host_out, out, 32 * n, hipMemcpyDeviceToHost, c.st));
+  HC(hipMemcpyAsync(hf, flags, 64, hipMemcpyDeviceToHost, c.st));
+  c.sync();
+  const uint32_t miss = hf[0], bad_sel = hf[1];
+  c.reset_staging();
+  if (bad_sel != 0xFFFFFFFFu) throw KgsError(KGS_E_ARG, "selF is not binary at row " + std::to_string(bad_sel) + ".");
+  if (miss != 0xFFFFFFFFu) throw KgsError(KGS_E_NOT_IN_TABLE, "Row " + std::to_string(miss) + " of F is not in the table.");
+}
+
+static void lookup_check_args(kgs_ctx_t* ctx, int npols, uint64_t n, const void* f, const void* t, const void* out) {
+  if (!ctx || !f || !t || !out) throw KgsError(KGS_E_ARG, "NULL argument");
+  if (npols < 1 || npols > EB_MAX) throw KgsError(KGS_E_ARG, "npols must be in 1 .. " + std::to_string(EB_MAX));
+  if (n < 1 || n > (1ull << 28)) throw KgsError(KGS_E_ARG, "n must be in 1 .. 2^28");
+}
+
+extern "C" {
+
+int kgs_lookup_multiplicities_device(kgs_ctx_t* ctx, int npols, uint64_t n, const void* const* d_evals_f,
+                                     const void* const* d_evals_t, const void* d_sel_f, void* d_mul_t_mont) {
+  API_BEGIN
+  lookup_check_args(ctx, npols, n, d_evals_f, d_evals_t, d_mul_t_mont);
+  CTX_LOCK(ctx);
+  if (ctx->group) throw KgsError(KGS_E_ARG, "The multiplicities of a lookup are not computed on a context attached to a rank group.");
+  HC(hipSetDevice(ctx->device));
+  DrainOnError drain(ctx);
+  ctx->reset_staging();
+  LookupCols F{npols, {}}, T{npols, {}};
+  for (int i = 0; i < npols; i++) {
+    if (!d_evals_f[i] || !d_evals_t[i]) throw KgsError(KGS_E_ARG, "NULL argument");
+    F.col[i] = (const uint32_t*)d_evals_f[i];
+    T.col[i] = (const uint32_t*)d_evals_t[i];
+  }
+  lookup_multiplicities_impl(*ctx, n, F, T, (const uint32_t*)d_sel_f, (uint32_t*)d_mul_t_mont, nullptr);
+  API_END
+}
+
+int kgs_lookup_multiplicities(kgs_ctx_t* ctx, int npols, uint64_t n, const uint8_t* const* evals_f,
+                              const uint8_t* const* evals_t, const uint8_t* sel_f, uint8_t* mul_t_mont) {
+  API_BEGIN
+  lookup_check_args(ctx, npols, n, evals_f, evals_t, mul_t_mont);
+  CTX_LOCK(ctx);
+  if (ctx->group) throw KgsError(KGS_E_ARG, "The multiplicities of a lookup are not computed on a context attached to a rank group.");
+  HC(hipSetDevice(ctx->device));
+  DrainOnError drain(ctx);
+  ctx->reset_staging();
+  const size_t E = 32 * (size_t)n;
+  // F_0 .. F_{k-1}, T_0 .. T_{k-1}, selF, then the output
+  uint32_t* in = ctx->buf("lk_in", E * (2 * (size_t)npols + 2));
+  LookupCols F{npols, {}}, T{npols, {}};
+  for (int i = 0; i < npols; i++) {
+    if (!evals_f[i] || !evals_t[i]) throw KgsError(KGS_E_ARG, "NULL argument");
+    uint32_t* df = in + (E / 4) * (size_t)i;
+    uint32_t* dt = in + (E / 4) * (size_t)(npols + i);
+    HC(hipMemcpyAsync(df, evals_f[i], E, hipMemcpyHostToDevice, ctx->st));
+    HC(hipMemcpyAsync(dt, evals_t[i], E, hipMemcpyHostToDevice, ctx->st));
+    F.col[i] = df;
+    T.col[i] = dt;
+  }
+  uint32_t* dsel = nullptr;
+  if (sel_f) {
+    dsel = in + (E / 4) * (size_t)(2 * npols);
+    HC(hipMemcpyAsync(dsel, sel_f, E, hipMemcpyHostToDevice, ctx->st));
+  }
+  uint32_t* dout = in + (E / 4) * (size_t)(2 * npols + 1);
+  lookup_multiplicities_impl(*ctx, n, F, T, dsel, dout, mul_t_mont);
+  API_END
+}
+
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]) {
   host::keccak256(data, (size_t)len, out);
   return KGS_OK;

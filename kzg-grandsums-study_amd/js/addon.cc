@@ -297,7 +297,8 @@ struct Job {
   napi_deferred deferred = nullptr;
   kgs_ctx_t* ctx = nullptr;
   int op = 0;  // 0 = load ptau, 1 = prove, 2 = elementwise Fr map / transform (frOp),
-               // 3 = one distributed proof over a rank group (proveGroup), 4 = msmPoints
+               // 3 = one distributed proof over a rank group (proveGroup), 4 = msmPoints,
+               // 5 = the multiplicities of a lookup table (lookupMultiplicities)
   int rc = 0;
   std::string err;
   // load
@@ -436,6 +437,21 @@ static void job_execute(napi_env, void* data) {
       case 2: j->rc = kgs_fr_batch_inverse(j->ctx, j->in.p, j->out, n); break;
       default: j->rc = kgs_ntt(j->ctx, j->in.p, j->out, logm, j->fr_op == 4); break;
     }
+  } else if (j->op == 5) {
+    j->out_len = j->f[0].len;
+    j->out = out_alloc(j->out_len);
+    if (!j->out) {
+      j->rc = KGS_E_ARG;
+      j->err = "out of host memory";
+      return;
+    }
+    std::vector<const uint8_t*> fp, tp;
+    for (int i = 0; i < j->npols; i++) {
+      fp.push_back(j->f[i].p);
+      tp.push_back(j->t[i].p);
+    }
+    j->rc = kgs_lookup_multiplicities(j->ctx, j->npols, j->out_len / 32, fp.data(), tp.data(),
+                                      j->selected ? j->sf.p : nullptr, j->out);
   } else if (j->op == 3) {
     if (prepare_prove(j)) group_execute(j);
     return;
@@ -472,7 +488,7 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_value u;
     napi_get_undefined(env, &u);
     napi_resolve_deferred(env, j->deferred, u);
-  } else if (j->op == 2) {
+  } else if (j->op == 2 || j->op == 5) {
     napi_resolve_deferred(env, j->deferred, adopt_u8(env, j->out, j->out_len));
     j->out = nullptr;
   } else if (j->op == 4) {
@@ -650,6 +666,52 @@ static napi_value FrOp(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_fr_op");
 }
 
+// lookupMultiplicities(ctx, [F...], [T...], selF|null) -> Promise<Uint8Array>: the Montgomery
+// multiplicities of the table rows (kgs_lookup_multiplicities). F / T: k standard-form buffers of the
+// same number of 32 B elements, selF a Montgomery selector of that length; all borrowed (referenced,
+// not copied) until the job completes, as the prover's inputs are.
+static napi_value LookupMultiplicities(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 5;
+  j->ctx = get_ctx(env, argv[0]);
+  uint32_t nf = 0, nt = 0;
+  napi_get_array_length(env, argv[1], &nf);
+  napi_get_array_length(env, argv[2], &nt);
+  j->npols = (int)nf;
+  for (uint32_t i = 0; i < nf && nf == nt; i++) {
+    napi_value e;
+    napi_get_element(env, argv[1], i, &e);
+    j->f.push_back(view_of(env, e, j->refs));
+    napi_get_element(env, argv[2], i, &e);
+    j->t.push_back(view_of(env, e, j->refs));
+  }
+  if (argc > 3) {
+    napi_valuetype ty;
+    napi_typeof(env, argv[3], &ty);
+    if (ty != napi_null && ty != napi_undefined) {
+      j->selected = true;
+      j->sf = view_of(env, argv[3], j->refs);
+    }
+  }
+  bool ok = nf >= 1 && nf == nt;
+  const size_t E = ok ? j->f[0].len : 0;
+  ok = ok && E >= 32 && E % 32 == 0;
+  for (uint32_t i = 0; ok && i < nf; i++) ok = j->f[i].p && j->t[i].p && j->f[i].len == E && j->t[i].len == E;
+  if (ok && j->selected) ok = j->sf.p && j->sf.len == E;
+  if (!ok) {
+    for (napi_ref r : j->refs) napi_delete_reference(env, r);
+    delete j;
+    napi_throw_error(env, nullptr,
+                     "lookupMultiplicities: F and T must be two lists of the same number of buffers, each (and "
+                     "selF) holding the same number (>= 1) of 32-byte elements");
+    return nullptr;
+  }
+  return queue(env, j, "kgs_lookup_multiplicities");
+}
+
 // verifyPtau(kind, ptauPath, nbits, npols, selected, commitments(Uint8Array), evaluations(Uint8Array))
 // -> boolean (host-only pairing check, kgs_verify_ptau)
 static napi_value VerifyPtau(napi_env env, napi_callback_info info) {
@@ -817,6 +879,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"frOp", nullptr, FrOp, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"lookupMultiplicities", nullptr, LookupMultiplicities, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(desc) / sizeof(desc[0]), desc);
   return exports;

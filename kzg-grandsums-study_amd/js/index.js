@@ -10,6 +10,9 @@ module.exports = {
     mset_eq_kzg_grandproduct_verifier: require("./src/grandproduct/mset_eq_kzg_verifier"),
     lookup_kzg_grandsum_prover: require("./src/lookup/lookup_kzg_prover"),
     lookup_kzg_grandsum_verifier: require("./src/lookup/lookup_kzg_verifier"),
+    // the table's multiplicities from the witness and the table, and the prover that computes them itself
+    lookup_multiplicities: require("./src/lookup/lookup_multiplicities"),
+    lookup_kzg_grandsum_prover_from_table: require("./src/lookup/lookup_multiplicities").lookup_kzg_grandsum_prover_from_table,
     // the provers' log channel (the reference's logger.js lines): setLogger(logplease instance), setLogLevel
     logger: require("./src/logger"),
 };
