@@ -249,7 +249,9 @@ int kgs_proof_shape(int kind, int npols, int selected, int* n_commitments, int* 
  * and evaluation buffers in the fixed order kgs_prove writes (kgs_proof_shape; KGS_LOOKUP proofs
  * are checked with kind KGS_LOOKUP and selected = 1); tau_g2 = [tau]_2 as
  * 128 B LEM (the second point of ptau section 3, kgs_ptau_read_tau_g2). Returns 1 (valid), 0
- * (invalid: not on G1, evaluation >= r, or the pairing equation fails) or a negative error. */
+ * (invalid: not on G1, evaluation >= r, or the pairing equation fails) or a negative error.
+ * One proof per call, two Miller loops and a final exponentiation each: kgs_verify_batch below shares
+ * one pairing check between all proofs checked against the same [tau]_2. */
 int kgs_verify(int kind, int nbits, int npols, int selected, const uint8_t* commitments, const uint8_t* evaluations,
                const uint8_t tau_g2[128]);
 int kgs_verify_ptau(int kind, const char* ptau_path, int nbits, int npols, int selected, const uint8_t* commitments,
@@ -259,6 +261,58 @@ int kgs_verify_ptau(int kind, const char* ptau_path, int nbits, int npols, int s
  * (64 B, Montgomery; (0, 0) = infinity), Q_k: affine LEM G2 (128 B: x.c0, x.c1, y.c0, y.c1). Points
  * off their curve: KGS_E_ARG. Host only. */
 int kgs_pairing_eq(int npairs, const uint8_t* g1_lem, const uint8_t* g2_lem);
+
+/* ---- batch verifier: many proofs against one [tau]_2, one pairing check (DESIGN.md "Batch verifier").
+ * For each proof the verifier's equation is e(-A_i, [tau]_2) * e(B_i, [1]_2) == 1 with A_i, B_i short
+ * linear combinations of the proof's own commitments and the generator (Fr scalars from the transcript
+ * replay and the evaluations). The batch draws weights rho_i, folds rho_i * A_i and rho_i * B_i for
+ * every proof (independent work per proof: on the GPU of `ctx`, kgs_g1_lincomb below), sums them and
+ * performs ONE 2-pair pairing check e(-sum rho_i A_i, [tau]_2) * e(sum rho_i B_i, [1]_2) == 1.
+ *
+ * Weights (deterministic: a batch gives the same bytes on every run; LE32 = 4 bytes little-endian)
+ *   seed  = keccak256("kgs-verify-batch-v1" || tau_g2 (128 B) || LE32(count) || for each proof in order:
+ *           LE32(kind) || LE32(nbits) || LE32(npols) || LE32(selected) || commitments || evaluations)
+ *   rho_i = the first 16 bytes of keccak256(seed || LE32(i)) read as a little-endian integer; 0 -> 1
+ * Soundness: the weights are fixed by a hash of everything the check depends on, so (in the random-oracle
+ * model) they are independent of the proofs' pairing residues; if some proof of the batch fails its own
+ * equation, the weighted product is 1 for at most one value of that proof's weight given the others, so a
+ * batch holding an invalid proof passes the aggregate check with probability at most 2^-128.
+ *
+ * A proof with a commitment off G1 or an evaluation >= r (the structural checks of kgs_verify) is
+ * marked invalid first and contributes no term: only points on the curve are folded.
+ * If the aggregate check fails and valid_out != NULL, the invalid proofs are located by bisection over
+ * the per-proof folded points (host point additions and further pairing checks, never a second fold; a
+ * half whose sibling passes under a failing parent is known to fail without a check): with b invalid
+ * proofs, pairing_checks <= 1 + 2 b ceil(log2 count) and never more than 2 count - 1. With
+ * valid_out == NULL the call stops after the aggregate check. Verdicts equal kgs_verify's.
+ *
+ * Returns 1 (every proof valid), 0 (some proof invalid) or a negative KGS_E_*: a bad kind / nbits /
+ * npols, a KGS_LOOKUP proof without selectors, a NULL buffer or a tau_g2 off its curve give KGS_E_ARG
+ * as for kgs_verify; so does a context attached to a rank group. count == 0 returns 1.
+ * ctx == NULL folds on the host (no GPU is touched). With a context the call holds its mutex, uses
+ * device buffers of its own (sized by the number of terms; the SRS, the domain tables and the prover's
+ * work buffers are left as they are) and returns with nothing pending on the context's streams, on
+ * its error paths too (kgs_ctx_idle). The environment variable KGS_VERIFY_BATCH_FOLD = "gpu" | "host"
+ * forces where a call with a context folds (default: the GPU from 128 terms on, about a dozen proofs,
+ * the host below: the measured crossover; diag->on_gpu tells which). */
+typedef struct {
+  int kind, nbits, npols, selected;
+  const uint8_t* commitments; /* kgs_proof_shape order, 64 B affine LEM each */
+  const uint8_t* evaluations; /* 32 B Montgomery each */
+} kgs_proof_ref_t;
+typedef struct {           /* optional; every pointer member optional (NULL: not wanted) */
+  uint8_t* weights_out;    /* in: count x 32 B, receives rho_i in standard form LE */
+  uint8_t* folded_out;     /* in: count x 128 B, receives rho_i*A_i || rho_i*B_i, affine LEM; zeros for a
+                              structurally invalid proof */
+  uint32_t pairing_checks; /* out: 2-pair pairing checks performed */
+  uint32_t terms;          /* out: (scalar, point) terms folded */
+  int on_gpu;              /* out: 1 if the fold ran on the GPU */
+  double fold_ms, pairing_ms; /* out: wall clock of the fold and of all pairing checks */
+} kgs_batch_diag_t;
+int kgs_verify_batch(kgs_ctx_t* ctx, const kgs_proof_ref_t* proofs, int count, const uint8_t tau_g2[128],
+                     uint8_t* valid_out /* count bytes (1 valid, 0 invalid) or NULL */, kgs_batch_diag_t* diag);
+int kgs_verify_batch_ptau(kgs_ctx_t* ctx, const char* ptau_path, const kgs_proof_ref_t* proofs, int count,
+                          uint8_t* valid_out, kgs_batch_diag_t* diag);
 
 /* Per-proof timing of the last kgs_prove* call (milliseconds, host wall clock): [0..4] prover rounds
  * 1-5, [5] unused, and for kgs_prove (host buffers) [6] input copy into pinned staging, [7] the
@@ -312,6 +366,17 @@ int kgs_lookup_multiplicities(kgs_ctx_t* ctx, int npols, uint64_t n, const uint8
  * leave the GPU between the two calls. */
 int kgs_lookup_multiplicities_device(kgs_ctx_t* ctx, int npols, uint64_t n, const void* const* d_evals_f,
                                      const void* const* d_evals_t, const void* d_sel_f, void* d_mul_t_mont);
+/* Segmented G1 linear combination (the fold of kgs_verify_batch): out_lem[s] = sum over the terms t in
+ * [seg_off[s], seg_off[s + 1]) of scalar_t * P_t, for s < nseg. points_lem: affine LEM points on the
+ * curve, the zero point allowed (a point off the curve or with a coordinate >= q: KGS_E_ARG);
+ * scalars_std: 32 B little-endian STANDARD form each, any 256-bit integer; seg_off: nseg + 1
+ * non-decreasing term offsets starting at 0 (at most 2^26 terms and segments). An empty segment or a
+ * sum equal to the identity gives 64 zero bytes. ctx == NULL computes on the host; with a context, one
+ * thread per term does double-and-add on the GPU, one per segment sums, and the results are made
+ * affine by a batched inversion. No SRS is needed, none is touched. Same context contract as
+ * kgs_lookup_multiplicities (mutex, no rank group, idle on return). */
+int kgs_g1_lincomb(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, const uint64_t* seg_off,
+                   uint64_t nseg, uint8_t* out_lem);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 

@@ -42,6 +42,19 @@ class KgsError(RuntimeError):
 KGS_E_RANGE = -9
 
 
+class ProofRef(ctypes.Structure):
+    """kgs_proof_ref_t (include/kgs.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("nbits", ctypes.c_int), ("npols", ctypes.c_int), ("selected", ctypes.c_int),
+                ("commitments", ctypes.c_void_p), ("evaluations", ctypes.c_void_p)]
+
+
+class BatchDiag(ctypes.Structure):
+    """kgs_batch_diag_t (include/kgs.h)."""
+    _fields_ = [("weights_out", ctypes.c_void_p), ("folded_out", ctypes.c_void_p), ("pairing_checks", ctypes.c_uint32),
+                ("terms", ctypes.c_uint32), ("on_gpu", ctypes.c_int), ("fold_ms", ctypes.c_double),
+                ("pairing_ms", ctypes.c_double)]
+
+
 class RangeError(ValueError):
     """What the reference's JavaScript throws as a RangeError ("offset is out of bounds": its divZh on a
     zero quotient, polynomial.js:857,884) — raised in reference-quirks mode only (include/kgs.h
@@ -110,6 +123,12 @@ def lib():
         L.kgs_verify.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_u8p, c_u8p, c_u8p]
         L.kgs_verify_ptau.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_u8p,
                                       c_u8p]
+        L.kgs_verify_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(ProofRef), ctypes.c_int, c_u8p, c_u8p,
+                                       ctypes.POINTER(BatchDiag)]
+        L.kgs_verify_batch_ptau.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ProofRef), ctypes.c_int,
+                                            c_u8p, ctypes.POINTER(BatchDiag)]
+        L.kgs_g1_lincomb.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+                                     c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.kgs_ctx_set_reference_quirks.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -559,6 +578,15 @@ class Context:
         PT = (ctypes.c_void_p * k)(*d_t)
         _check(lib().kgs_lookup_multiplicities_device(self._h, k, n, PF, PT, d_sf, d_out))
 
+    def verify_batch(self, items, tau_g2=None, ptau=None, locate=True, diag=None):
+        """Batch verifier (kgs_verify_batch) with the fold on this context's GPU: see the module-level
+        verify_batch. Exactly one of tau_g2 (128 B LEM) and ptau (a file name) is given."""
+        return _verify_batch(self._h, items, tau_g2, ptau, locate, diag)
+
+    def g1_lincomb(self, points_lem, scalars_std, seg_off):
+        """Segmented G1 linear combination on the GPU (kgs_g1_lincomb): see the module-level g1_lincomb."""
+        return _g1_lincomb(self._h, points_lem, scalars_std, seg_off)
+
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
         sent, host all-gather count / wall ms / bytes sent; zeros after a single-GPU proof."""
@@ -894,24 +922,115 @@ def _verifier(kind, pTauFilename, proof, nBits):
     """src/{grandsum,grandproduct}/mset_eq_kzg_verifier.js:9 — the proof's shape is read from its
     keys as the reference does (nPols from /^F[0-9]/, selectors from /^selF/); the check runs in
     libkgs (kgs_verify_ptau: transcript replay + optimal-ate pairing, host only)."""
+    shape = _proof_buffers(kind, proof)
+    if shape is None:
+        return False
+    npols, selected, com, ev = shape
+    rc = _check(lib().kgs_verify_ptau(kind, os.fsencode(pTauFilename), nBits, npols, 1 if selected else 0,
+                                      _buf(com), _buf(ev)))
+    return rc == 1
+
+
+def _proof_buffers(kind, proof):
+    """(npols, selected, commitments, evaluations) of a proof dict in the C-ABI order, its shape read
+    from its keys; None for a proof that is invalid before the library sees it (a missing key, a value
+    of the wrong length, a lookup without selectors)."""
     import re
     keys = list(proof["commitments"].keys())
     nfi = len([k for k in keys if re.match(r"^F\d", k)])
     npols = nfi if nfi > 0 else 1
     selected = len([k for k in keys if re.match(r"^selF", k)]) == 1
     if kind == LOOKUP and not selected:
-        return False
+        return None
     cn, en = proof_names(kind, npols, selected)
     try:
         com = b"".join(bytes(proof["commitments"][n]) for n in cn)
         ev = b"".join(bytes(proof["evaluations"][n]) for n in en)
     except KeyError:
-        return False
+        return None
     if len(com) != 64 * len(cn) or len(ev) != 32 * len(en):
-        return False
-    rc = _check(lib().kgs_verify_ptau(kind, os.fsencode(pTauFilename), nBits, npols, 1 if selected else 0,
-                                      _buf(com), _buf(ev)))
-    return rc == 1
+        return None
+    return npols, selected, com, ev
+
+
+def _verify_batch(handle, items, tau_g2, ptau, locate, diag):
+    if (tau_g2 is None) == (ptau is None):
+        raise ValueError("give exactly one of tau_g2 and ptau")
+    items = list(items)
+    sent = []  # positions of the items that reach the library
+    keep = []
+    for pos, (kind, proof, nBits) in enumerate(items):
+        shape = _proof_buffers(kind, proof)
+        if shape is not None:
+            sent.append(pos)
+            keep.append((kind, nBits) + shape)
+    n = len(sent)
+    refs = (ProofRef * max(n, 1))()
+    bufs = []
+    for j, (kind, nBits, npols, selected, com, ev) in enumerate(keep):
+        cb, eb = _buf(com), _buf(ev)
+        bufs += [cb, eb]
+        refs[j] = ProofRef(kind, nBits, npols, 1 if selected else 0, ctypes.cast(cb, ctypes.c_void_p),
+                           ctypes.cast(eb, ctypes.c_void_p))
+    valid = ctypes.create_string_buffer(max(n, 1)) if locate else None
+    d = BatchDiag()
+    w = f = None
+    if diag is not None:
+        w, f = ctypes.create_string_buffer(32 * max(n, 1)), ctypes.create_string_buffer(128 * max(n, 1))
+        d.weights_out, d.folded_out = ctypes.cast(w, ctypes.c_void_p), ctypes.cast(f, ctypes.c_void_p)
+    if ptau is not None:
+        rc = lib().kgs_verify_batch_ptau(handle, os.fsencode(ptau), refs, n, valid, ctypes.byref(d))
+    else:
+        rc = lib().kgs_verify_batch(handle, refs, n, _buf(tau_g2), valid, ctypes.byref(d))
+    _check(rc)
+    if diag is not None:
+        diag.update(indices=sent, weights=w.raw[:32 * n], folded=f.raw[:128 * n], pairing_checks=d.pairing_checks,
+                    terms=d.terms, on_gpu=d.on_gpu, fold_ms=d.fold_ms, pairing_ms=d.pairing_ms)
+    if not locate:
+        return rc == 1 and n == len(items)
+    out = [False] * len(items)
+    for j, pos in enumerate(sent):
+        out[pos] = valid.raw[j] == 1
+    return out
+
+
+def verify_batch(pTauFilename, items, device=0, locate=True, diag=None):
+    """Verify many proofs against one ptau's [tau]_2 with ONE pairing check (include/kgs.h
+    kgs_verify_batch). items: a sequence of (kind, proof, nBits) with kind GRANDSUM / GRANDPRODUCT /
+    LOOKUP and proof the dict the provers return; each proof's shape is read from its keys as the
+    single-proof verifiers do. Returns a list of bool, item for item what grandsum_verifier /
+    grandproduct_verifier / lookup_verifier return; an item with a missing key, a value of the wrong
+    length or a lookup without selectors is False without reaching the library.
+    device: the GPU whose context folds the proofs' commitments; None folds on the host (no GPU).
+    locate=False stops after the aggregate check and returns one bool (all valid).
+    diag: a dict that receives indices (positions of the items sent to the library; the entries below
+    are in that order), weights (32 B each), folded (128 B each: rho A || rho B), pairing_checks, terms,
+    on_gpu, fold_ms, pairing_ms."""
+    handle = None if device is None else _context(device).handle
+    return _verify_batch(handle, items, None, pTauFilename, locate, diag)
+
+
+def _g1_lincomb(handle, points_lem, scalars_std, seg_off):
+    seg_off = list(seg_off)
+    if not seg_off:
+        raise ValueError("seg_off holds the number of segments + 1 offsets")
+    nseg = len(seg_off) - 1
+    nterms = seg_off[-1]
+    if len(points_lem) != 64 * nterms or len(scalars_std) != 32 * nterms:
+        raise ValueError("points_lem / scalars_std must hold seg_off[-1] points of 64 B / scalars of 32 B")
+    off = (ctypes.c_uint64 * (nseg + 1))(*seg_off)
+    out = ctypes.create_string_buffer(max(64 * nseg, 1))
+    _check(lib().kgs_g1_lincomb(handle, _buf(points_lem), _buf(scalars_std), off, nseg, out))
+    return out.raw[:64 * nseg]
+
+
+def g1_lincomb(points_lem, scalars_std, seg_off, device=0):
+    """out[s] = sum over t in [seg_off[s], seg_off[s + 1]) of scalars[t] * points[t] (kgs_g1_lincomb):
+    points 64 B affine LEM (the zero point allowed), scalars 32 B little-endian standard form (any
+    256-bit integer), seg_off the nseg + 1 term offsets. Returns nseg x 64 B affine LEM (zeros for the
+    identity). device=None computes on the host."""
+    handle = None if device is None else _context(device).handle
+    return _g1_lincomb(handle, points_lem, scalars_std, seg_off)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

@@ -1,4 +1,4 @@
-// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip). All pointers are device
+// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip). All pointers are device
 // pointers to 32 B Montgomery Fr elements (uint32_t[8]) or 64 B affine / 128 B XYZZ G1 points,
 // unless stated otherwise. Launches are asynchronous on `st`.
 #pragma once
@@ -151,6 +151,15 @@ struct LookupCols {
 void launch_lookup_multiplicities(hipStream_t st, uint32_t* out, uint32_t* table, uint64_t capacity, uint32_t* count,
                                   uint32_t* flags, const LookupCols& F, const LookupCols& T, const uint32_t* sel_f,
                                   uint64_t n);
+
+// fold.hip
+// out_aff[s] (64 B affine LEM, zeros for the identity) = sum_{t in [seg_off[s], seg_off[s + 1])} scalars[t] * points[t]
+// for s < nseg. points: nterms affine LEM points on the curve (zero allowed); scalars: nterms x 8 words,
+// STANDARD form, any 256-bit integer; seg_off: nseg + 1 non-decreasing term offsets, seg_off[nseg] == nterms.
+// Work buffers: term_xyzz 128 B x nterms, seg_xyzz 128 B x nseg, scratch 32 B x nseg.
+void launch_g1_fold(hipStream_t st, uint32_t* out_aff, const uint32_t* points, const uint32_t* scalars,
+                    const uint32_t* seg_off, uint64_t nterms, uint64_t nseg, uint32_t* term_xyzz, uint32_t* seg_xyzz,
+                    uint32_t* scratch);
 
 // msm.hip
 void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int W, uint32_t* tmp_xyzz,

@@ -17,59 +17,17 @@
 #include "host_field.hpp"
 #include "host_pairing.hpp"
 #include "transcript.hpp"
+#include "verify_linear.hpp"
 
 using namespace kgs;
 using host::Fq;
 using host::Fr;
 using host::G1;
+using host::Proof;  // proof layout, lt_mod, g1_valid: verify_linear.hpp (shared with verify_batch.cpp)
+using host::g1_valid;
+using host::lt_mod;
 
 namespace {
-
-bool lt_mod(const uint8_t* le, const uint64_t* p) {  // little-endian 256-bit value < p
-  for (int i = 3; i >= 0; i--) {
-    uint64_t w;
-    memcpy(&w, le + 8 * i, 8);
-    if (w != p[i]) return w < p[i];
-  }
-  return false;
-}
-
-// G1.isValid on an affine LEM point: infinity, or canonical coordinates on y^2 = x^3 + 3
-bool g1_valid(const uint8_t* lem) {
-  bool zero = true;
-  for (int i = 0; i < 64; i++) zero &= lem[i] == 0;
-  if (zero) return true;
-  if (!lt_mod(lem, host::FQ_MOD.p) || !lt_mod(lem + 32, host::FQ_MOD.p)) return false;
-  Fq x = Fq::from_bytes(lem), y = Fq::from_bytes(lem + 32);
-  return y.sqr() == x.sqr() * x + Fq::from_u64(3);
-}
-
-struct Proof {
-  int npols;
-  bool sel, gs;
-  const uint8_t* com;  // fixed order (kgs_proof_shape)
-  const uint8_t* ev;
-  bool lookup = false;  // KGS_LOOKUP: no binary constraint on selT
-  // commitment indices
-  const uint8_t* F(int i) const { return com + 64 * (2 * i); }
-  const uint8_t* T(int i) const { return com + 64 * (2 * i + 1); }
-  const uint8_t* selF() const { return com + 64 * (2 * npols); }
-  const uint8_t* selT() const { return com + 64 * (2 * npols + 1); }
-  int base() const { return 2 * npols + (sel ? 2 : 0); }
-  const uint8_t* S() const { return com + 64 * base(); }  // S (grand-sum) or Z (grand-product)
-  const uint8_t* Q() const { return com + 64 * (base() + 1); }
-  const uint8_t* Wxi() const { return com + 64 * (base() + 2); }
-  const uint8_t* Wxiw() const { return com + 64 * (base() + 3); }
-  int ncom() const { return base() + 4; }
-  // evaluation indices: per pol f (and t for grand-sum), then selF, selT, then S(xi w) / Z(xi w)
-  int per() const { return gs ? 2 : 1; }
-  const uint8_t* fxi_raw(int i) const { return ev + 32 * (per() * i); }
-  const uint8_t* txi_raw(int i) const { return ev + 32 * (per() * i + 1); }
-  const uint8_t* selFxi_raw() const { return ev + 32 * (per() * npols); }
-  const uint8_t* selTxi_raw() const { return ev + 32 * (per() * npols + 1); }
-  const uint8_t* sxiw_raw() const { return ev + 32 * (per() * npols + (sel ? 2 : 0)); }
-  int nev() const { return per() * npols + (sel ? 2 : 0) + 1; }
-};
 
 Fr fr_at(const uint8_t* b) { return Fr::from_bytes(b); }
 G1 pt(const uint8_t* lem) { return G1::from_affine_lem(lem); }

@@ -1,0 +1,259 @@
+// The verifiers' pairing equation as a linear form (host only, no GPU): shared by verifier.cpp
+// (kgs_verify) and verify_batch.cpp (kgs_verify_batch, kgs_g1_lincomb).
+//
+// For a proof of ncom commitments C_0 .. C_{ncom-1} (fixed order of kgs_proof_shape) the check of
+// src/{grandsum,grandproduct}/mset_eq_kzg_verifier.js is e(-A, [tau]2) * e(B, [1]2) == 1 with
+//   A = 1 * Wxi + u * Wxiw
+//   B = sum_j b_j * C_j + b_G * G1
+// where every b_j and b_G is an element of Fr computed from the transcript challenges and the
+// proof's evaluations alone. linear_form() does the structural checks, the transcript replay and
+// that Fr arithmetic, and returns the scalars; no point is touched beyond the on-curve check.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "host_field.hpp"
+#include "transcript.hpp"
+
+namespace kgs {
+namespace host {
+
+inline bool lt_mod(const uint8_t* le, const uint64_t* p) {  // little-endian 256-bit value < p
+  for (int i = 3; i >= 0; i--) {
+    uint64_t w;
+    memcpy(&w, le + 8 * i, 8);
+    if (w != p[i]) return w < p[i];
+  }
+  return false;
+}
+
+// G1.isValid on an affine LEM point: infinity, or canonical coordinates on y^2 = x^3 + 3
+inline bool g1_valid(const uint8_t* lem) {
+  bool zero = true;
+  for (int i = 0; i < 64; i++) zero &= lem[i] == 0;
+  if (zero) return true;
+  if (!lt_mod(lem, FQ_MOD.p) || !lt_mod(lem + 32, FQ_MOD.p)) return false;
+  Fq x = Fq::from_bytes(lem), y = Fq::from_bytes(lem + 32);
+  return y.sqr() == x.sqr() * x + Fq::from_u64(3);
+}
+
+inline void g1_gen_lem(uint8_t out[64]) {
+  Fq::one().to_bytes(out);
+  Fq::from_u64(2).to_bytes(out + 32);
+}
+
+struct Proof {
+  int npols;
+  bool sel, gs;
+  const uint8_t* com;  // fixed order (kgs_proof_shape)
+  const uint8_t* ev;
+  bool lookup = false;  // KGS_LOOKUP: no binary constraint on selT
+  // commitment indices
+  int iF(int i) const { return 2 * i; }
+  int iT(int i) const { return 2 * i + 1; }
+  int iselF() const { return 2 * npols; }
+  int iselT() const { return 2 * npols + 1; }
+  int base() const { return 2 * npols + (sel ? 2 : 0); }
+  int iS() const { return base(); }  // S (grand-sum) or Z (grand-product)
+  int iQ() const { return base() + 1; }
+  int iWxi() const { return base() + 2; }
+  int iWxiw() const { return base() + 3; }
+  int ncom() const { return base() + 4; }
+  const uint8_t* C(int j) const { return com + 64 * (size_t)j; }
+  const uint8_t* F(int i) const { return C(iF(i)); }
+  const uint8_t* T(int i) const { return C(iT(i)); }
+  const uint8_t* selF() const { return C(iselF()); }
+  const uint8_t* selT() const { return C(iselT()); }
+  const uint8_t* S() const { return C(iS()); }
+  const uint8_t* Q() const { return C(iQ()); }
+  const uint8_t* Wxi() const { return C(iWxi()); }
+  const uint8_t* Wxiw() const { return C(iWxiw()); }
+  // evaluation indices: per pol f (and t for grand-sum), then selF, selT, then S(xi w) / Z(xi w)
+  int per() const { return gs ? 2 : 1; }
+  const uint8_t* fxi_raw(int i) const { return ev + 32 * (size_t)(per() * i); }
+  const uint8_t* txi_raw(int i) const { return ev + 32 * (size_t)(per() * i + 1); }
+  const uint8_t* selFxi_raw() const { return ev + 32 * (size_t)(per() * npols); }
+  const uint8_t* selTxi_raw() const { return ev + 32 * (size_t)(per() * npols + 1); }
+  const uint8_t* sxiw_raw() const { return ev + 32 * (size_t)(per() * npols + (sel ? 2 : 0)); }
+  int nev() const { return per() * npols + (sel ? 2 : 0) + 1; }
+};
+
+// validateCommitments / validateEvaluations (grandsum verifier.js:194-244, grandproduct :200-233)
+inline bool proof_structure_ok(const Proof& p) {
+  for (int i = 0; i < p.ncom(); i++)
+    if (!g1_valid(p.C(i))) return false;
+  for (int i = 0; i < p.nev(); i++)
+    if (!lt_mod(p.ev + 32 * (size_t)i, FR_MOD.p)) return false;
+  return true;
+}
+
+// fr_w(k) for k <= 28, computed once (fr_w raises 5 to a 226-bit power on every call)
+inline const Fr& fr_w_cached(int k) {
+  static const std::vector<Fr> tab = [] {
+    std::vector<Fr> t(29);
+    t[28] = fr_w(28);
+    for (int s = 27; s >= 0; s--) t[s] = t[s + 1].sqr();
+    return t;
+  }();
+  return tab[k];
+}
+
+struct LinearForm {
+  Fr a_wxi, a_wxiw;   // A = a_wxi * Wxi + a_wxiw * Wxiw
+  std::vector<Fr> b;  // B = sum_j b[j] * C_j + b_g * G1, j in the commitment order of the proof
+  Fr b_g;
+};
+
+// The scalars of a structurally valid proof (proof_structure_ok). Follows verify_impl of verifier.cpp
+// line by line; every point operation there becomes an addition into the coefficient of its point.
+inline LinearForm linear_form(const Proof& p, int nbits) {
+  const int k = p.npols;
+  const bool vec = k > 1;
+  auto fr_at = [](const uint8_t* b) { return Fr::from_bytes(b); };
+  // computeChallenges (grandsum verifier.js:246-312)
+  Transcript tr;
+  for (int i = 0; i < k; i++) {
+    tr.add_commitment(p.F(i));
+    tr.add_commitment(p.T(i));
+  }
+  if (p.sel) {
+    tr.add_commitment(p.selF());
+    tr.add_commitment(p.selT());
+  }
+  Fr beta = Fr::zero();
+  if (vec) {
+    beta = tr.challenge();
+    tr.add_scalar(beta);
+  }
+  const Fr gamma = tr.challenge();
+  tr.add_scalar(gamma);
+  tr.add_commitment(p.S());
+  const Fr alpha = tr.challenge();
+  tr.add_scalar(alpha);
+  tr.add_commitment(p.Q());
+  const Fr xi = tr.challenge();
+  tr.add_scalar(xi);
+  for (int i = 0; i < k; i++) {
+    tr.add_scalar(fr_at(p.fxi_raw(i)));
+    if (p.gs) tr.add_scalar(fr_at(p.txi_raw(i)));
+  }
+  if (p.sel) {
+    tr.add_scalar(fr_at(p.selFxi_raw()));
+    tr.add_scalar(fr_at(p.selTxi_raw()));
+  }
+  const Fr sxiw = fr_at(p.sxiw_raw());
+  tr.add_scalar(sxiw);
+  const Fr v = tr.challenge();
+  tr.add_scalar(v);
+  tr.add_commitment(p.Wxi());
+  tr.add_commitment(p.Wxiw());
+  const Fr u = tr.challenge();
+
+  // Z_H(xi), L1(xi) (polynomial_utils.js:1-19)
+  Fr xn = xi;
+  for (int i = 0; i < nbits; i++) xn = xn.sqr();
+  const Fr zh = xn - Fr::one();
+  const Fr l1 = zh * (Fr::from_u64(1ull << nbits) * (xi - Fr::one())).inverse();
+  const Fr w = fr_w_cached(nbits);
+
+  LinearForm lf;
+  lf.b.assign(p.ncom(), Fr::zero());
+  Fr r0 = Fr::zero();
+  Fr selF = Fr::zero(), selT = Fr::zero();
+  if (p.sel) {
+    selF = fr_at(p.selFxi_raw());
+    selT = fr_at(p.selTxi_raw());
+    if (!p.lookup) r0 = r0 + (selT - selT.sqr());  // a lookup's selT holds multiplicities
+    r0 = r0 * alpha;
+    r0 = (r0 + (selF - selF.sqr())) * alpha;
+  }
+  Fr fxi = Fr::zero(), txi = Fr::zero();
+  for (int i = k - 1; i >= 0; i--) {
+    fxi = fxi * beta + fr_at(p.fxi_raw(i));
+    if (p.gs) txi = txi * beta + fr_at(p.txi_raw(i));
+  }
+  // [D]1 = d11 * S - Z_H * Q (+ D12 for the grand-product), with coefficient v^0 in [F]1
+  if (p.gs) {
+    const Fr fg = fxi + gamma, tg = txi + gamma;
+    Fr r01 = sxiw * (fg * tg);
+    if (p.sel)
+      r01 = r01 + selT * fg - selF * tg;
+    else
+      r01 = r01 + fxi - txi;
+    r0 = (r0 + r01) * alpha;
+    lf.b[p.iS()] = (l1 - alpha * fg * tg) + u;
+  } else {
+    Fr r01 = sxiw;
+    r01 = p.sel ? r01 * ((gamma - Fr::one()) * selT + Fr::one()) : r01 * gamma;
+    r0 = (r0 + r01) * alpha;
+    r0 = r0 - l1;
+    Fr fg = fxi + gamma;
+    if (p.sel) fg = (fg - Fr::one()) * selF + Fr::one();
+    lf.b[p.iS()] = (l1 - alpha * fg) + u;
+    // D12 = alpha * sxiw * [selT(xi)] * sum_i beta^i T_i
+    Fr c = sxiw * alpha;
+    if (p.sel) c = c * selT;
+    for (int i = 0; i < k; i++) {
+      lf.b[p.iT(i)] = lf.b[p.iT(i)] + c;
+      c = c * beta;
+    }
+  }
+  lf.b[p.iQ()] = zh.neg();
+  // [F]1 (grandsum verifier.js:125-142) and [E]1 (:146-167): v^(i+1) on F_i and f_i(xi), then the
+  // T_i / t_i(xi) of a grand-sum, then selF, selT
+  Fr E = u * sxiw - r0;
+  Fr pw = v;
+  for (int i = 0; i < k; i++) {
+    lf.b[p.iF(i)] = lf.b[p.iF(i)] + pw;
+    E = E + pw * fr_at(p.fxi_raw(i));
+    pw = pw * v;
+  }
+  if (p.gs)
+    for (int i = 0; i < k; i++) {
+      lf.b[p.iT(i)] = lf.b[p.iT(i)] + pw;
+      E = E + pw * fr_at(p.txi_raw(i));
+      pw = pw * v;
+    }
+  if (p.sel) {
+    lf.b[p.iselF()] = lf.b[p.iselF()] + pw;
+    E = E + pw * selF;
+    pw = pw * v;
+    lf.b[p.iselT()] = lf.b[p.iselT()] + pw;
+    E = E + pw * selT;
+  }
+  lf.b_g = E.neg();
+  // pairing equation (:170-186)
+  lf.a_wxi = Fr::one();
+  lf.a_wxiw = u;
+  lf.b[p.iWxi()] = xi;
+  lf.b[p.iWxiw()] = u * xi * w;
+  return lf;
+}
+
+// sum_t s_t * P_t over one segment (Straus: the terms share the doublings). Points are affine LEM on
+// the curve (or zero), scalars 32 B little-endian standard form, any 256-bit integer.
+inline G1 g1_lincomb_segment(const uint8_t* points_lem, const uint8_t* scalars_std, size_t nterms) {
+  std::vector<G1> pts(nterms);
+  int top = -1;
+  for (size_t t = 0; t < nterms; t++) {
+    pts[t] = G1::from_affine_lem(points_lem + 64 * t);
+    if (pts[t].is_inf()) continue;
+    for (int i = 255; i > top; i--)
+      if ((scalars_std[32 * t + (i >> 3)] >> (i & 7)) & 1) {
+        top = i;
+        break;
+      }
+  }
+  G1 acc = G1::inf();
+  for (int i = top; i >= 0; i--) {
+    acc = acc.dbl();
+    for (size_t t = 0; t < nterms; t++)
+      if ((scalars_std[32 * t + (i >> 3)] >> (i & 7)) & 1) acc = acc.add(pts[t]);
+  }
+  return acc;
+}
+
+}  // namespace host
+}  // namespace kgs

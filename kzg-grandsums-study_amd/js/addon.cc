@@ -299,6 +299,7 @@ struct Job {
   int op = 0;  // 0 = load ptau, 1 = prove, 2 = elementwise Fr map / transform (frOp),
                // 3 = one distributed proof over a rank group (proveGroup), 4 = msmPoints,
                // 5 = the multiplicities of a lookup table (lookupMultiplicities)
+               // 6 = a batch of proofs against one ptau (verifyBatch)
   int rc = 0;
   std::string err;
   // load
@@ -321,6 +322,11 @@ struct Job {
   // msmPoints: bases and standard-form scalars (copied: the call returns before the work runs)
   std::vector<uint8_t> bases, scal;
   uint8_t msm_out[64];
+  // verifyBatch: the proofs' shapes and bytes (copied), the verdicts and the call's diagnostics
+  std::vector<kgs_proof_ref_t> vb_refs;
+  std::vector<std::vector<uint8_t>> vb_bytes;
+  std::vector<uint8_t> vb_valid;
+  kgs_batch_diag_t vb_diag = {};
   // frOp
   int fr_op = 0;
   View in;
@@ -452,6 +458,11 @@ static void job_execute(napi_env, void* data) {
     }
     j->rc = kgs_lookup_multiplicities(j->ctx, j->npols, j->out_len / 32, fp.data(), tp.data(),
                                       j->selected ? j->sf.p : nullptr, j->out);
+  } else if (j->op == 6) {
+    j->vb_valid.assign(j->vb_refs.size() + 1, 0);
+    const int rc = kgs_verify_batch_ptau(j->ctx, j->path.c_str(), j->vb_refs.data(), (int)j->vb_refs.size(),
+                                         j->vb_valid.data(), &j->vb_diag);
+    j->rc = rc < 0 ? rc : KGS_OK;
   } else if (j->op == 3) {
     if (prepare_prove(j)) group_execute(j);
     return;
@@ -493,6 +504,21 @@ static void job_complete(napi_env env, napi_status, void* data) {
     j->out = nullptr;
   } else if (j->op == 4) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->msm_out, 64));
+  } else if (j->op == 6) {
+    napi_value o, v;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "valid", make_u8(env, j->vb_valid.data(), j->vb_refs.size()));
+    napi_create_uint32(env, j->vb_diag.pairing_checks, &v);
+    napi_set_named_property(env, o, "pairingChecks", v);
+    napi_create_uint32(env, j->vb_diag.terms, &v);
+    napi_set_named_property(env, o, "terms", v);
+    napi_get_boolean(env, j->vb_diag.on_gpu != 0, &v);
+    napi_set_named_property(env, o, "onGpu", v);
+    napi_create_double(env, j->vb_diag.fold_ms, &v);
+    napi_set_named_property(env, o, "foldMs", v);
+    napi_create_double(env, j->vb_diag.pairing_ms, &v);
+    napi_set_named_property(env, o, "pairingMs", v);
+    napi_resolve_deferred(env, j->deferred, o);
   } else {
     napi_value o, arr;
     napi_create_object(env, &o);
@@ -712,6 +738,57 @@ static napi_value LookupMultiplicities(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_lookup_multiplicities");
 }
 
+// verifyBatch(ctx, ptauPath, [{kind, nbits, npols, selected, commitments(Uint8Array), evaluations(Uint8Array)}, ..])
+// -> Promise<{valid: Uint8Array (1 / 0 per proof), pairingChecks, terms, onGpu, foldMs, pairingMs}>
+// (kgs_verify_batch_ptau: one pairing check for the batch, the G1 fold on the context's GPU). The
+// proofs' bytes are copied: the call returns before the work runs.
+static napi_value VerifyBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 6;
+  j->ctx = get_ctx(env, argv[0]);
+  size_t plen = 0;
+  napi_get_value_string_utf8(env, argv[1], nullptr, 0, &plen);
+  j->path.assign(plen + 1, '\0');
+  napi_get_value_string_utf8(env, argv[1], &j->path[0], plen + 1, &plen);
+  j->path.resize(plen);
+  uint32_t n = 0;
+  napi_get_array_length(env, argv[2], &n);
+  bool ok = true;
+  j->vb_bytes.reserve(2 * (size_t)n);
+  for (uint32_t i = 0; i < n && ok; i++) {
+    napi_value e, v;
+    napi_get_element(env, argv[2], i, &e);
+    int32_t kind = 0, nbits = 0, npols = 0;
+    bool selected = false;
+    napi_get_named_property(env, e, "kind", &v);
+    napi_get_value_int32(env, v, &kind);
+    napi_get_named_property(env, e, "nbits", &v);
+    napi_get_value_int32(env, v, &nbits);
+    napi_get_named_property(env, e, "npols", &v);
+    napi_get_value_int32(env, v, &npols);
+    napi_get_named_property(env, e, "selected", &v);
+    napi_get_value_bool(env, v, &selected);
+    napi_get_named_property(env, e, "commitments", &v);
+    j->vb_bytes.push_back(bytes_of(env, v));
+    napi_get_named_property(env, e, "evaluations", &v);
+    j->vb_bytes.push_back(bytes_of(env, v));
+    int nc = 0, ne = 0;
+    ok = kgs_proof_shape(kind, npols, selected ? 1 : 0, &nc, &ne) == KGS_OK &&
+         j->vb_bytes[2 * i].size() == (size_t)nc * 64 && j->vb_bytes[2 * i + 1].size() == (size_t)ne * 32;
+    j->vb_refs.push_back(kgs_proof_ref_t{kind, nbits, npols, selected ? 1 : 0, j->vb_bytes[2 * i].data(),
+                                         j->vb_bytes[2 * i + 1].data()});
+  }
+  if (!ok) {
+    delete j;
+    napi_throw_error(env, nullptr, "verifyBatch: proof buffers do not match the proof shape");
+    return nullptr;
+  }
+  return queue(env, j, "kgs_verify_batch");
+}
+
 // verifyPtau(kind, ptauPath, nbits, npols, selected, commitments(Uint8Array), evaluations(Uint8Array))
 // -> boolean (host-only pairing check, kgs_verify_ptau)
 static napi_value VerifyPtau(napi_env env, napi_callback_info info) {
@@ -880,6 +957,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"frOp", nullptr, FrOp, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lookupMultiplicities", nullptr, LookupMultiplicities, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"verifyBatch", nullptr, VerifyBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(desc) / sizeof(desc[0]), desc);
   return exports;

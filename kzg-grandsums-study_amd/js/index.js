@@ -13,6 +13,8 @@ module.exports = {
     // the table's multiplicities from the witness and the table, and the prover that computes them itself
     lookup_multiplicities: require("./src/lookup/lookup_multiplicities"),
     lookup_kzg_grandsum_prover_from_table: require("./src/lookup/lookup_multiplicities").lookup_kzg_grandsum_prover_from_table,
+    // many proofs against one ptau, one pairing check (kgs_verify_batch)
+    kzg_verifier_batch: require("./src/verifier_batch"),
     // the provers' log channel (the reference's logger.js lines): setLogger(logplease instance), setLogLevel
     logger: require("./src/logger"),
 };
