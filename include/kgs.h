@@ -314,6 +314,71 @@ int kgs_verify_batch(kgs_ctx_t* ctx, const kgs_proof_ref_t* proofs, int count, c
 int kgs_verify_batch_ptau(kgs_ctx_t* ctx, const char* ptau_path, const kgs_proof_ref_t* proofs, int count,
                           uint8_t* valid_out, kgs_batch_diag_t* diag);
 
+/* ---- multi-argument proofs: m arguments over one domain, one quotient, one pair of openings
+ * (the reference's TODO "run in the case of multiple arguments (of any kind) at the same
+ * time"). Argument j (0 <= j < m, 1 <= m <= KGS_MAX_ARGS) has its own kind (KGS_GRANDSUM,
+ * KGS_GRANDPRODUCT or KGS_LOOKUP), number of columns and selectors, in any mix; all share the domain
+ * 2^nbits. The arguments share beta (drawn if any of them is a vector argument), gamma, alpha, xi, v and
+ * u; a separator delta, drawn after alpha when m > 1, weights argument j's quotient numerator N_j and
+ * linearisation r_j by delta^j:
+ *   Q     = (sum_j delta^j N_j) / Z_H
+ *   W_xi  opens r = sum_j delta^j r_j - Z_H(xi) Q and every round-1 polynomial at xi (v^1, v^2, .. in
+ *         proof order: per argument the F's, the T's of a grand-sum / lookup, then selF, selT)
+ *   W_xiw opens sum_j v^j S_j at xi w
+ * so m arguments cost 3 commitments of n points each plus ONE Q, W_xi and W_xiw (about 3 n m + 5 n MSM
+ * points against 8 n m for m single proofs), the proof holds sum_j (2 k_j + 2 sel_j) + m + 3 points
+ * and is checked by one pairing equation. With m = 1 no delta is drawn and the proof is byte for byte
+ * kgs_prove's in exact-math mode.
+ *   commitments_out  every argument's round-1 commitments, argument by argument in kgs_prove's order
+ *                    (F0,T0,..,[selF,selT]), then S_0 .. S_{m-1} (Z for a grand-product), Q, Wxi, Wxiw
+ *   evaluations_out  every argument's evaluations at xi, argument by argument in kgs_prove's order
+ *                    (f0,t0,.. for a grand-sum / lookup, f0,.. for a grand-product, [selF,selT]), then
+ *                    S_0(xi w) .. S_{m-1}(xi w)
+ * Transcript: all round-1 commitments in that order -> [beta, absorbed] -> gamma; gamma, S_0 .. S_{m-1}
+ * -> alpha; [alpha -> delta]; delta (alpha when m = 1), Q -> xi; xi, the evaluations in that order -> v;
+ * v, Wxi, Wxiw -> u.
+ * The prover is always exact-math (as for KGS_LOOKUP there is no reference behaviour to follow:
+ * kgs_ctx_set_reference_quirks has no effect on it). Context contract of the provers: the call holds the
+ * context's mutex and returns with nothing pending on its streams, on its error paths too
+ * (kgs_ctx_idle). kgs_prove_multi takes host pointers and stages them with plain copies (no pipelined
+ * staging, and no Montgomery write-back: that is a side effect of the reference's single provers);
+ * kgs_prove_multi_device takes device pointers on ctx's device.
+ * Failures: the codes of kgs_prove. An argument's own failure carries the reference's message prefixed
+ * with "argument <j>: " for the lowest failing j: KGS_E_NOT_WELL_CALC ("The grand-sum polynomial S is not
+ * well calculated" / its grand-product form), KGS_E_NOT_DIVISIBLE ("Polynomial is not divisible"), and
+ * the KGS_E_ARG of a bad kind or npols or of a lookup without selectors. KGS_E_DOES_NOT_DIVIDE
+ * ("Polynomial does not divide") belongs to the shared openings and names no argument; KGS_E_SRS keeps
+ * the reference's SRS message. KGS_E_ARG also for count outside 1 .. KGS_MAX_ARGS, an nbits outside
+ * 1 .. 28 or above the nbits_max the SRS was loaded for, a context attached to a rank group
+ * (kgs_ctx_set_group) and a context with MSM sharding switched on (kgs_ctx_set_shard). */
+#define KGS_MAX_ARGS 16
+typedef struct {
+  int kind, npols, selected;
+} kgs_arg_shape_t;
+typedef struct {
+  int kind, npols;
+  const void* const* evals_f; /* npols pointers, n x 32 B STANDARD form each */
+  const void* const* evals_t;
+  const void* sel_f; /* n x 32 B MONTGOMERY, or both NULL (unselected) */
+  const void* sel_t;
+} kgs_arg_t;
+/* number of commitments / evaluations of a multi-argument proof of these shapes */
+int kgs_multi_proof_shape(const kgs_arg_shape_t* args, int count, int* n_commitments, int* n_evaluations);
+int kgs_prove_multi(kgs_ctx_t* ctx, int nbits, const kgs_arg_t* args, int count, uint8_t* commitments_out,
+                    uint8_t* evaluations_out);
+int kgs_prove_multi_device(kgs_ctx_t* ctx, int nbits, const kgs_arg_t* args, int count, uint8_t* commitments_out,
+                           uint8_t* evaluations_out);
+/* Verifier of a multi-argument proof (host only, as kgs_verify): 1 (valid), 0 (invalid: a commitment not
+ * on G1, an evaluation >= r, or the pairing equation e(-A, [tau]_2) e(B, [1]_2) == 1 fails) or a negative
+ * code (KGS_E_ARG: a bad count, kind, npols or nbits, a lookup without selectors, a NULL buffer, a tau_g2
+ * off its curve). A = Wxi + u Wxiw; B = the per-argument terms of kgs_verify's equation weighted by
+ * delta^j, u v^j on each S_j, xi Wxi + u xi w Wxiw and the evaluations' scalar multiple of the generator.
+ * With count = 1 the verdict is kgs_verify's. */
+int kgs_verify_multi(int nbits, const kgs_arg_shape_t* args, int count, const uint8_t* commitments,
+                     const uint8_t* evaluations, const uint8_t tau_g2[128]);
+int kgs_verify_multi_ptau(const char* ptau_path, int nbits, const kgs_arg_shape_t* args, int count,
+                          const uint8_t* commitments, const uint8_t* evaluations);
+
 /* Per-proof timing of the last kgs_prove* call (milliseconds, host wall clock): [0..4] prover rounds
  * 1-5, [5] unused, and for kgs_prove (host buffers) [6] input copy into pinned staging, [7] the
  * prover, [8] wait for the Montgomery write-back to the caller. Returns the number written. */

@@ -55,6 +55,20 @@ class BatchDiag(ctypes.Structure):
                 ("pairing_ms", ctypes.c_double)]
 
 
+MAX_ARGS = 16
+
+
+class ArgShape(ctypes.Structure):
+    """kgs_arg_shape_t (include/kgs.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("npols", ctypes.c_int), ("selected", ctypes.c_int)]
+
+
+class Arg(ctypes.Structure):
+    """kgs_arg_t (include/kgs.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("npols", ctypes.c_int), ("evals_f", ctypes.POINTER(ctypes.c_void_p)),
+                ("evals_t", ctypes.POINTER(ctypes.c_void_p)), ("sel_f", ctypes.c_void_p), ("sel_t", ctypes.c_void_p)]
+
+
 class RangeError(ValueError):
     """What the reference's JavaScript throws as a RangeError ("offset is out of bounds": its divZh on a
     zero quotient, polynomial.js:857,884) — raised in reference-quirks mode only (include/kgs.h
@@ -127,6 +141,13 @@ def lib():
                                        ctypes.POINTER(BatchDiag)]
         L.kgs_verify_batch_ptau.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ProofRef), ctypes.c_int,
                                             c_u8p, ctypes.POINTER(BatchDiag)]
+        L.kgs_multi_proof_shape.argtypes = [ctypes.POINTER(ArgShape), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                            ctypes.POINTER(ctypes.c_int)]
+        L.kgs_prove_multi.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Arg), ctypes.c_int, c_u8p, c_u8p]
+        L.kgs_prove_multi_device.argtypes = L.kgs_prove_multi.argtypes
+        L.kgs_verify_multi.argtypes = [ctypes.c_int, ctypes.POINTER(ArgShape), ctypes.c_int, c_u8p, c_u8p, c_u8p]
+        L.kgs_verify_multi_ptau.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ArgShape), ctypes.c_int, c_u8p,
+                                            c_u8p]
         L.kgs_g1_lincomb.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
                                      c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -669,6 +690,79 @@ class Context:
                 [ev.raw[32 * i:32 * i + 32] for i in range(ne.value)])
 
 
+    def _prove_multi(self, fn, nbits, args, ptr):
+        m = len(args)
+        recs = (Arg * max(m, 1))()
+        shapes, keep = [], []
+        for j, (kind, fs, ts, sf, st) in enumerate(args):
+            k = len(fs)
+            PF = (ctypes.c_void_p * max(k, 1))()
+            PT = (ctypes.c_void_p * max(k, 1))()
+            for i in range(min(k, len(ts))):
+                (PF[i], kf), (PT[i], kt) = ptr(fs[i]), ptr(ts[i])
+                keep += [kf, kt]
+            psf = pst = None
+            if sf is not None:
+                (psf, k1), (pst, k2) = ptr(sf), ptr(st)
+                keep += [k1, k2]
+            keep += [PF, PT]
+            recs[j] = Arg(kind, k, PF, PT, psf, pst)
+            shapes.append((kind, k, sf is not None))
+        try:
+            nc, ne = multi_proof_shape(shapes)
+        except KgsError:
+            nc = ne = 1  # the prover rejects these shapes below, with its own message, before it writes
+        com = ctypes.create_string_buffer(64 * nc)
+        ev = ctypes.create_string_buffer(32 * ne)
+        _check(fn(self._h, nbits, recs, m, com, ev))
+        return [com.raw[64 * i:64 * i + 64] for i in range(nc)], [ev.raw[32 * i:32 * i + 32] for i in range(ne)]
+
+    def prove_multi(self, nbits, args):
+        """Multi-argument prover on host buffers (kgs_prove_multi): args is a list of
+        (kind, evals_f, evals_t, sel_f, sel_t) with evals_f / evals_t lists of standard-form buffers of
+        2^nbits 32-byte elements and sel_f / sel_t Montgomery buffers or both None. Inputs are read in
+        place and left as they are. Returns (commitment list, evaluation list) in the order of kgs.h."""
+        n = 1 << nbits
+        for a in args:
+            bufs = list(a[1]) + list(a[2]) + [x for x in a[3:5] if x is not None]
+            if any(len(x) != 32 * n for x in bufs):
+                raise ValueError("evaluation buffers must hold 2^nbits 32-byte elements")
+            if (a[3] is None) != (a[4] is None):
+                raise ValueError("selectors must be both given or both None")
+        return self._prove_multi(lib().kgs_prove_multi, nbits, args, _ptr)
+
+    def prove_multi_device(self, nbits, args):
+        """Device-resident twin (kgs_prove_multi_device): the same tuples with device pointers (ints)."""
+        return self._prove_multi(lib().kgs_prove_multi_device, nbits, args, lambda p: (p, None))
+
+
+def multi_proof_shape(shapes):
+    """(commitments, evaluations) of a multi-argument proof (kgs_multi_proof_shape); shapes is a list of
+    (kind, npols, selected)."""
+    arr = (ArgShape * max(len(shapes), 1))(*[ArgShape(k, p, 1 if s else 0) for k, p, s in shapes])
+    nc, ne = ctypes.c_int(), ctypes.c_int()
+    rc = lib().kgs_multi_proof_shape(arr, len(shapes), ctypes.byref(nc), ctypes.byref(ne))
+    if rc < 0:
+        raise KgsError(rc, "bad multi-argument shapes")
+    return nc.value, ne.value
+
+
+def proof_names_multi(shapes):
+    """Commitment / evaluation key order of a multi-argument proof (kgs.h): shapes is a list of
+    (kind, npols, selected). One argument: proof_names's. More: every argument's names prefixed with
+    "A<j>." ("A0.F", "A1.T2", "A1.selF", "A0.S", "A1.Z", "A0.fxi", "A1.zxiw"); Q, Wxi, Wxiw keep theirs."""
+    if len(shapes) == 1:
+        return proof_names(*shapes[0])
+    com, com_s, ev, ev_s = [], [], [], []
+    for j, (kind, npols, selected) in enumerate(shapes):
+        cn, en = proof_names(kind, npols, selected)
+        com += [f"A{j}.{x}" for x in cn[:-4]]
+        com_s.append(f"A{j}.{cn[-4]}")
+        ev += [f"A{j}.{x}" for x in en[:-1]]
+        ev_s.append(f"A{j}.{en[-1]}")
+    return com + com_s + ["Q", "Wxi", "Wxiw"], ev + ev_s
+
+
 def dist_exchange_model(kind, nbits, npols, selected, world):
     """All-to-alls of one distributed proof (csrc/prover_dist.cpp) and the bytes that
     leave each rank in them: round 1 one per F_i / T_i (+ selectors) at n; round 2 S BLOCK -> E and its
@@ -715,11 +809,9 @@ def _context(device=0):
     return _CTX[device]
 
 
-def _prover(kind, pTauFilename, evalsFs, evalsTs, evalsSelF=None, evalsSelT=None, device=0):
-    """src/grandsum/mset_eq_kzg_prover.js:12-142 — input checks with the reference's messages, then
-    the HIP prover. Overwrites evalsFs[i].eval / evalsTs[i].eval with Montgomery form (:147-148)."""
-    log.info("> MULTISET EQUALITY KZG %s PROVER STARTED", _TITLE[kind])
-    power = ptau_power(pTauFilename)  # the header is read first (prover.js:15-16)
+def _prover_inputs(kind, power, evalsFs, evalsTs, evalsSelF, evalsSelT):
+    """src/grandsum/mset_eq_kzg_prover.js:22-81 — the input checks with the reference's messages.
+    -> (evalsFs, evalsTs, evalsSelF, evalsSelT, is_selected, nbits)"""
     if not isinstance(evalsFs, (list, tuple)):
         evalsFs = [evalsFs]
     if not isinstance(evalsTs, (list, tuple)):
@@ -754,6 +846,17 @@ def _prover(kind, pTauFilename, evalsFs, evalsTs, evalsSelF=None, evalsSelT=None
         raise ValueError("Polynomial length must be a power of two.")
     if power < nbits:
         raise ValueError("The Powers of Tau file is not sufficiently large to commit the polynomials.")
+    return evalsFs, evalsTs, evalsSelF, evalsSelT, is_selected, nbits
+
+
+def _prover(kind, pTauFilename, evalsFs, evalsTs, evalsSelF=None, evalsSelT=None, device=0):
+    """src/grandsum/mset_eq_kzg_prover.js:12-142 — input checks with the reference's messages, then
+    the HIP prover. Overwrites evalsFs[i].eval / evalsTs[i].eval with Montgomery form (:147-148)."""
+    log.info("> MULTISET EQUALITY KZG %s PROVER STARTED", _TITLE[kind])
+    power = ptau_power(pTauFilename)  # the header is read first (prover.js:15-16)
+    evalsFs, evalsTs, evalsSelF, evalsSelT, is_selected, nbits = _prover_inputs(kind, power, evalsFs, evalsTs,
+                                                                                evalsSelF, evalsSelT)
+    npols = len(evalsFs)
     if log.isEnabledFor(logging.INFO):  # prover.js:87-93
         for line in ("-------------------------------------", f"  MULTISET EQUALITY KZG {_TITLE[kind]} PROVER SETTINGS",
                      "  Curve:       bn128", f"  Domain size: {1 << nbits}", f"  Number of polynomials: {npols}",
@@ -1107,3 +1210,67 @@ def lookup_verifier(pTauFilename, proof, nBits):
     """Verifier of lookup_prover's proofs: the grand-sum verifier (src/grandsum/mset_eq_kzg_verifier.js:9)
     without the selT-binary term of r0 (:80-81)."""
     return _verifier(LOOKUP, pTauFilename, proof, nBits)
+
+
+def _multi_arg(a):
+    """One argument of multi_prover: a dict {"kind", "evalsFs", "evalsTs", "evalsSelF", "evalsSelT"} (the
+    selectors optional; a lookup's multiplicities go in "evalsSelT") or the same as a tuple."""
+    if isinstance(a, dict):
+        return a["kind"], a["evalsFs"], a["evalsTs"], a.get("evalsSelF"), a.get("evalsSelT")
+    a = tuple(a)
+    return a + (None,) * (5 - len(a))
+
+
+def multi_prover(pTauFilename, args, device=0):
+    """One proof of several arguments over one domain (include/kgs.h kgs_prove_multi): the
+    arguments share their challenges, one quotient and one pair of opening proofs. args: a list of 1 ..
+    16 arguments (_multi_arg), each of kind GRANDSUM / GRANDPRODUCT / LOOKUP with the Evaluations the
+    single provers take. Every argument passes the single provers' input checks (same messages, prefixed
+    with "argument <j>: "). The inputs are left as they are (no Montgomery write-back). Returns the
+    proof dict with the names of proof_names_multi."""
+    log.info("> MULTI-ARGUMENT KZG PROVER STARTED")
+    power = ptau_power(pTauFilename)
+    args = [_multi_arg(a) for a in args]
+    if not 1 <= len(args) <= MAX_ARGS:
+        raise ValueError(f"The number of arguments must be in 1 .. {MAX_ARGS}.")
+    recs, shapes, nbits = [], [], None
+    for j, (kind, fs, ts, sf, st) in enumerate(args):
+        if kind not in (GRANDSUM, GRANDPRODUCT, LOOKUP):
+            raise ValueError(f"argument {j}: unknown argument kind")
+        try:
+            fs, ts, sf, st, selected, nb = _prover_inputs(kind, power, fs, ts, sf, st)
+        except ValueError as e:
+            raise ValueError(f"argument {j}: {e}") from None
+        if nbits is not None and nb != nbits:
+            raise ValueError(f"argument {j}: every argument must have the domain of argument 0.")
+        nbits = nb
+        recs.append((kind, [e.eval for e in fs], [e.eval for e in ts], sf.eval if selected else None,
+                     st.eval if selected else None))
+        shapes.append((kind, len(fs), selected))
+    ctx = _context(device)
+    ctx.load_ptau(pTauFilename, nbits)
+    try:
+        coms, evs = ctx.prove_multi(nbits, recs)
+    except KgsError as e:
+        raise _semantic(e) from e
+    cn, en = proof_names_multi(shapes)
+    log.info("> MULTI-ARGUMENT KZG PROVER FINISHED")
+    return {"commitments": dict(zip(cn, coms)), "evaluations": dict(zip(en, evs))}
+
+
+def multi_verifier(pTauFilename, proof, nBits, shapes):
+    """Verifier of multi_prover's proofs (kgs_verify_multi_ptau; host only): shapes is the list of
+    (kind, npols, selected) the proof was made for. False for a proof with a missing key or a value of the
+    wrong length."""
+    shapes = [tuple(s) for s in shapes]
+    cn, en = proof_names_multi(shapes)
+    try:
+        com = b"".join(bytes(proof["commitments"][x]) for x in cn)
+        ev = b"".join(bytes(proof["evaluations"][x]) for x in en)
+    except KeyError:
+        return False
+    if len(com) != 64 * len(cn) or len(ev) != 32 * len(en):
+        return False
+    arr = (ArgShape * len(shapes))(*[ArgShape(k, p, 1 if s else 0) for k, p, s in shapes])
+    rc = _check(lib().kgs_verify_multi_ptau(os.fsencode(pTauFilename), nBits, arr, len(shapes), _buf(com), _buf(ev)))
+    return rc == 1

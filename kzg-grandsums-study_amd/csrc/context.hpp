@@ -417,6 +417,8 @@ struct Commit {
 };
 void shard_range(uint64_t n, int rank, int world, uint64_t& lo, uint64_t& hi);
 void fork_lanes(kgs_ctx& c);
+// work issued on `to` after this waits for everything issued on `from` so far
+void lane_join(kgs_ctx& c, hipStream_t from, hipStream_t to);
 Commit commit_launch(kgs_ctx& c, const uint32_t* scalars, uint64_t N, int slot, int lane = 0);
 // latency mode (two MSM lanes, one unsharded context): points [0, cut) on lane 0 and [cut, N) on
 // lane 1 (slots slot, slot + 1); the two partials are summed by commits_finish. Otherwise the same

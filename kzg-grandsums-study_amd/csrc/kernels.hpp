@@ -101,6 +101,24 @@ void launch_builder(hipStream_t st, bool prod, bool sel, uint32_t* out, const ui
 void launch_quotient(hipStream_t st, bool prod, bool sel, uint32_t* q, const uint32_t* S, const uint32_t* F,
                      const uint32_t* T, const uint32_t* SF, const uint32_t* ST, const uint32_t* inv_nxm1,
                      const uint32_t* scalars, int lcs, uint32_t rot);
+// The quotient of a multi-argument proof (prover_multi.cpp): up to QM_MAX arguments per launch share the
+// coset point, the Z_H and L1 factors and the store. Argument j contributes delta^j times its numerator.
+constexpr int QM_MAX = 8;
+struct QuotArg {
+  const uint32_t *S, *F, *T, *SF, *ST;  // coset evaluations, bit-reversed (SF / ST: selected only)
+  int prod, sel, lookup;                // grand-product / selected / no selT-binary term
+  uint32_t delta[8];                    // delta^j
+  uint32_t delta29[LC_W29];             // delta^j as a 29-bit record (prover.cpp fr29_record)
+};
+struct QuotMulti {
+  int nargs;
+  int accumulate;  // add to q instead of overwriting it (the launches after the first of m > QM_MAX)
+  QuotArg a[QM_MAX];
+};
+// q[p] (+)= (alpha / Z_H)(x_p) * sum_j delta^j core_j(x_p) + inv_nxm1[p] * sum_j delta^j l1op_j(x_p), with core_j /
+// l1op_j what launch_quotient computes for argument j alone; scalars, lcs, rot as for launch_quotient
+void launch_quotient_multi(hipStream_t st, uint32_t* q, const QuotMulti& qm, const uint32_t* inv_nxm1,
+                           const uint32_t* scalars, int lcs, uint32_t rot);
 void launch_divcheck(hipStream_t st, bool prod, bool sel, uint32_t* flag, const uint32_t* S, const uint32_t* f,
                      const uint32_t* t, const uint32_t* sf, const uint32_t* stt, const uint32_t* scalars, uint64_t n,
                      const uint32_t* S_next = nullptr, uint64_t gbase = 0);

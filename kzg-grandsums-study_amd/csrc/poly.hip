@@ -429,6 +429,59 @@ void launch_quotient(hipStream_t st, bool prod, bool sel, uint32_t* q, const uin
 #undef KGS_Q
 }
 
+// Multi-argument quotient (prover_multi.cpp): Q = (sum_j delta^j N_j) / Z_H for up to QM_MAX arguments per
+// launch, each with its own kind and selectors. Per coset point the arguments' cores and L1 operands are
+// weighted by delta^j (29-bit products, lazy sums on [0, 2p)) and summed in registers; alpha / Z_H and
+// 1/(n(x - 1)) multiply the two sums once and q is stored once. The descriptor comes by value (kernarg),
+// so an argument's pointers, kind and flags are scalar loads and the kind branch is uniform over the
+// grid. A streaming kernel: 3-5 loads of 32 B per argument and point against ~10 products.
+template <bool PROD, bool SEL>
+__device__ __forceinline__ void quotient_multi_arg(fr& accC, fr& accL, const QuotArg& a, uint64_t p, uint64_t pj,
+                                                   const fr& alpha, const fr& gamma) {
+  const fr s = fr::load(a.S + 8 * p), sw = fr::load(a.S + 8 * pj);
+  const fr sf = SEL ? fr::load(a.SF + 8 * p) : fr::zero(), st = SEL ? fr::load(a.ST + 8 * p) : fr::zero();
+  const fr core = quotient_core_na<PROD, SEL>(s, sw, fr::load(a.F + 8 * p), fr::load(a.T + 8 * p), sf, st, alpha, gamma,
+                                              SEL && !a.lookup ? alpha : fr::zero());
+  W29 d;
+#pragma unroll
+  for (int j = 0; j < 9; j++) d.l[j] = a.delta29[j];
+  accC = fr::add_lazy(accC, mul29(core, d));
+  accL = fr::add_lazy(accL, mul29(PROD ? s - fr::one() : s, d));
+}
+
+__global__ void __launch_bounds__(256) k_quotient_multi(uint32_t* __restrict__ q, QuotMulti qm,
+                                                        const uint32_t* __restrict__ inv_nxm1,
+                                                        const uint32_t* __restrict__ sc, int lcs, uint32_t rot) {
+  KGS_AUX_PRIO();
+  const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t cs = 1ull << lcs;
+  if (p >= cs) return;
+  const fr alpha = fr::load(sc), gamma = fr::load(sc + 8);
+  const uint32_t i = brev((uint32_t)p, lcs);
+  const uint32_t j = (i + rot) & (uint32_t)(cs - 1);
+  const uint64_t pj = brev(j, lcs);
+  fr accC = fr::zero(), accL = fr::zero();
+  for (int k = 0; k < qm.nargs; k++) {
+    const QuotArg& a = qm.a[k];
+    if (a.prod) {
+      if (a.sel) quotient_multi_arg<true, true>(accC, accL, a, p, pj, alpha, gamma);
+      else quotient_multi_arg<true, false>(accC, accL, a, p, pj, alpha, gamma);
+    } else {
+      if (a.sel) quotient_multi_arg<false, true>(accC, accL, a, p, pj, alpha, gamma);
+      else quotient_multi_arg<false, false>(accC, accL, a, p, pj, alpha, gamma);
+    }
+  }
+  const W29 az = w29_load(sc + ((rot == 2 && (i & 1)) ? 56 : 40));
+  fr out = fr::reduce_once(mul29(accC, az)) + fr::reduce_once(accL) * fr::load(inv_nxm1 + 8 * p);
+  if (qm.accumulate) out = out + fr::load(q + 8 * p);
+  out.store(q + 8 * p);
+}
+
+void launch_quotient_multi(hipStream_t st, uint32_t* q, const QuotMulti& qm, const uint32_t* inv_nxm1,
+                           const uint32_t* scalars, int lcs, uint32_t rot) {
+  hipLaunchKernelGGL(k_quotient_multi, dim3(nb(1ull << lcs)), dim3(256), 0, st, q, qm, inv_nxm1, scalars, lcs, rot);
+}
+
 // Divisibility of the quotient numerator by Z_H, evaluated on H (natural order): N(w^i) == 0.
 // S_next: S at the natural index following the last one of this array (the wrap S[0] on one GPU,
 // the next rank's first element when H is BLOCK-distributed); gbase: natural index of element 0.

@@ -163,6 +163,31 @@ bool verify_impl(const Proof& p, int nbits, const host::G2A& tau_g2) {
 
 thread_local std::string v_err;
 
+// kgs_verify_multi: the shapes as a MultiProof, or false for a bad count / kind / npols / lookup shape
+bool multi_shape(const kgs_arg_shape_t* args, int count, host::MultiProof& p) {
+  if (!args || count < 1 || count > KGS_MAX_ARGS) return false;
+  for (int j = 0; j < count; j++) {
+    const kgs_arg_shape_t& a = args[j];
+    if (a.kind != KGS_GRANDSUM && a.kind != KGS_GRANDPRODUCT && a.kind != KGS_LOOKUP) return false;
+    if (a.kind == KGS_LOOKUP && !a.selected) return false;
+    if (a.npols < 1 || a.npols > (1 << 20)) return false;
+    p.args.push_back({a.npols, a.selected != 0, a.kind != KGS_GRANDPRODUCT, a.kind == KGS_LOOKUP});
+  }
+  return true;
+}
+
+// e(-A, [tau]2) * e(B, [1]2) == 1 with A, B from the proof's linear form (verify_linear.hpp)
+bool verify_multi_impl(const host::MultiProof& p, int nbits, const host::G2A& tau_g2) {
+  if (!host::multi_structure_ok(p)) return false;
+  const host::LinearForm lf = host::linear_form_multi(p, nbits);
+  const G1 A = pt(p.C(p.iWxi())).mul(lf.a_wxi).add(pt(p.C(p.iWxiw())).mul(lf.a_wxiw));
+  uint8_t g1gen[64];
+  host::g1_gen_lem(g1gen);
+  G1 B = pt(g1gen).mul(lf.b_g);
+  for (int i = 0; i < p.ncom(); i++) B = B.add(pt(p.C(i)).mul(lf.b[i]));
+  return host::pairing_eq2(A.neg(), tau_g2, B, host::g2_gen());
+}
+
 }  // namespace
 
 extern "C" {
@@ -189,6 +214,36 @@ int kgs_verify(int kind, int nbits, int npols, int selected, const uint8_t* comm
   } catch (const std::exception&) {
     return KGS_E_ARG;
   }
+}
+
+int kgs_multi_proof_shape(const kgs_arg_shape_t* args, int count, int* n_commitments, int* n_evaluations) {
+  host::MultiProof p{{}, nullptr, nullptr};
+  if (!multi_shape(args, count, p)) return KGS_E_ARG;
+  if (n_commitments) *n_commitments = p.ncom();
+  if (n_evaluations) *n_evaluations = p.nev();
+  return KGS_OK;
+}
+
+int kgs_verify_multi(int nbits, const kgs_arg_shape_t* args, int count, const uint8_t* commitments,
+                     const uint8_t* evaluations, const uint8_t tau_g2[128]) {
+  if (nbits < 1 || nbits > 28 || !commitments || !evaluations || !tau_g2) return KGS_E_ARG;
+  try {
+    host::MultiProof p{{}, commitments, evaluations};
+    if (!multi_shape(args, count, p)) return KGS_E_ARG;
+    host::G2A t2 = host::g2_from_lem(tau_g2);
+    if (!host::g2_on_curve(t2)) return KGS_E_ARG;
+    return verify_multi_impl(p, nbits, t2) ? 1 : 0;
+  } catch (const std::exception&) {
+    return KGS_E_ARG;
+  }
+}
+
+int kgs_verify_multi_ptau(const char* ptau_path, int nbits, const kgs_arg_shape_t* args, int count,
+                          const uint8_t* commitments, const uint8_t* evaluations) {
+  uint8_t t2[128];
+  int rc = kgs_ptau_read_tau_g2(ptau_path, t2);
+  if (rc < 0) return rc;
+  return kgs_verify_multi(nbits, args, count, commitments, evaluations, t2);
 }
 
 int kgs_pairing_eq(int npairs, const uint8_t* g1_lem, const uint8_t* g2_lem) {

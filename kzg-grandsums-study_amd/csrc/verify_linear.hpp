@@ -232,6 +232,172 @@ inline LinearForm linear_form(const Proof& p, int nbits) {
   return lf;
 }
 
+// ---- multi-argument proofs (kgs_verify_multi; layout and transcript in include/kgs.h)
+struct ArgShape {
+  int npols;
+  bool sel, gs, lookup;
+  int ncom1() const { return 2 * npols + (sel ? 2 : 0); }           // round-1 commitments
+  int nev() const { return (gs ? 2 : 1) * npols + (sel ? 2 : 0); }  // evaluations at xi
+};
+struct MultiProof {
+  std::vector<ArgShape> args;
+  const uint8_t* com;
+  const uint8_t* ev;
+  int m() const { return (int)args.size(); }
+  int ncom1() const {
+    int s = 0;
+    for (const ArgShape& a : args) s += a.ncom1();
+    return s;
+  }
+  int nev_xi() const {
+    int s = 0;
+    for (const ArgShape& a : args) s += a.nev();
+    return s;
+  }
+  int iS(int j) const { return ncom1() + j; }
+  int iQ() const { return ncom1() + m(); }
+  int iWxi() const { return iQ() + 1; }
+  int iWxiw() const { return iQ() + 2; }
+  int ncom() const { return iQ() + 3; }
+  int nev() const { return nev_xi() + m(); }
+  const uint8_t* C(int i) const { return com + 64 * (size_t)i; }
+  const uint8_t* E(int i) const { return ev + 32 * (size_t)i; }
+};
+
+inline bool multi_structure_ok(const MultiProof& p) {
+  for (int i = 0; i < p.ncom(); i++)
+    if (!g1_valid(p.C(i))) return false;
+  for (int i = 0; i < p.nev(); i++)
+    if (!lt_mod(p.E(i), FR_MOD.p)) return false;
+  return true;
+}
+
+// The scalars of a structurally valid multi-argument proof: per argument exactly linear_form's terms
+// under the shared challenges, weighted by delta^j; the openings' powers of v run over all arguments.
+inline LinearForm linear_form_multi(const MultiProof& p, int nbits) {
+  const int m = p.m();
+  auto fr_at = [](const uint8_t* b) { return Fr::from_bytes(b); };
+  bool any_vec = false;
+  for (const ArgShape& a : p.args) any_vec |= a.npols > 1;
+  Transcript tr;
+  for (int i = 0; i < p.ncom1(); i++) tr.add_commitment(p.C(i));
+  Fr beta = Fr::zero();
+  if (any_vec) {
+    beta = tr.challenge();
+    tr.add_scalar(beta);
+  }
+  const Fr gamma = tr.challenge();
+  tr.add_scalar(gamma);
+  for (int j = 0; j < m; j++) tr.add_commitment(p.C(p.iS(j)));
+  const Fr alpha = tr.challenge();
+  tr.add_scalar(alpha);
+  Fr delta = Fr::one();
+  if (m > 1) {
+    delta = tr.challenge();
+    tr.add_scalar(delta);
+  }
+  tr.add_commitment(p.C(p.iQ()));
+  const Fr xi = tr.challenge();
+  tr.add_scalar(xi);
+  for (int i = 0; i < p.nev(); i++) tr.add_scalar(fr_at(p.E(i)));
+  const Fr v = tr.challenge();
+  tr.add_scalar(v);
+  tr.add_commitment(p.C(p.iWxi()));
+  tr.add_commitment(p.C(p.iWxiw()));
+  const Fr u = tr.challenge();
+
+  Fr xn = xi;
+  for (int i = 0; i < nbits; i++) xn = xn.sqr();
+  const Fr zh = xn - Fr::one();
+  const Fr l1 = zh * (Fr::from_u64(1ull << nbits) * (xi - Fr::one())).inverse();
+  const Fr w = fr_w_cached(nbits);
+
+  LinearForm lf;
+  lf.b.assign(p.ncom(), Fr::zero());
+  Fr E = Fr::zero();  // b_g = -E
+  Fr dj = Fr::one(), vj = Fr::one(), pw = v;
+  int c0 = 0, e0 = 0;  // argument j's first commitment / evaluation
+  for (int j = 0; j < m; j++) {
+    const ArgShape& a = p.args[j];
+    const int k = a.npols, per = a.gs ? 2 : 1;
+    auto fx = [&](int i) { return fr_at(p.E(e0 + per * i)); };
+    auto tx = [&](int i) { return fr_at(p.E(e0 + per * i + 1)); };
+    const int iF0 = c0, iselF = c0 + 2 * k, eSel = e0 + per * k;
+    const Fr sxiw = fr_at(p.E(p.nev_xi() + j));
+    Fr r0 = Fr::zero();
+    Fr selF = Fr::zero(), selT = Fr::zero();
+    if (a.sel) {
+      selF = fr_at(p.E(eSel));
+      selT = fr_at(p.E(eSel + 1));
+      if (!a.lookup) r0 = r0 + (selT - selT.sqr());
+      r0 = r0 * alpha;
+      r0 = (r0 + (selF - selF.sqr())) * alpha;
+    }
+    Fr fxi = Fr::zero(), txi = Fr::zero();
+    for (int i = k - 1; i >= 0; i--) {
+      fxi = fxi * beta + fx(i);
+      if (a.gs) txi = txi * beta + tx(i);
+    }
+    Fr bS;
+    if (a.gs) {
+      const Fr fg = fxi + gamma, tg = txi + gamma;
+      Fr r01 = sxiw * (fg * tg);
+      if (a.sel)
+        r01 = r01 + selT * fg - selF * tg;
+      else
+        r01 = r01 + fxi - txi;
+      r0 = (r0 + r01) * alpha;
+      bS = l1 - alpha * fg * tg;
+    } else {
+      Fr r01 = sxiw;
+      r01 = a.sel ? r01 * ((gamma - Fr::one()) * selT + Fr::one()) : r01 * gamma;
+      r0 = (r0 + r01) * alpha;
+      r0 = r0 - l1;
+      Fr fg = fxi + gamma;
+      if (a.sel) fg = (fg - Fr::one()) * selF + Fr::one();
+      bS = l1 - alpha * fg;
+      Fr c = sxiw * alpha * dj;
+      if (a.sel) c = c * selT;
+      for (int i = 0; i < k; i++) {
+        lf.b[iF0 + 2 * i + 1] = lf.b[iF0 + 2 * i + 1] + c;
+        c = c * beta;
+      }
+    }
+    lf.b[p.iS(j)] = dj * bS + u * vj;
+    E = E + u * vj * sxiw - dj * r0;
+    for (int i = 0; i < k; i++) {
+      lf.b[iF0 + 2 * i] = lf.b[iF0 + 2 * i] + pw;
+      E = E + pw * fx(i);
+      pw = pw * v;
+    }
+    if (a.gs)
+      for (int i = 0; i < k; i++) {
+        lf.b[iF0 + 2 * i + 1] = lf.b[iF0 + 2 * i + 1] + pw;
+        E = E + pw * tx(i);
+        pw = pw * v;
+      }
+    if (a.sel) {
+      lf.b[iselF] = lf.b[iselF] + pw;
+      E = E + pw * selF;
+      pw = pw * v;
+      lf.b[iselF + 1] = lf.b[iselF + 1] + pw;
+      E = E + pw * selT;
+      pw = pw * v;
+    }
+    c0 += a.ncom1();
+    e0 += a.nev();
+    dj = dj * delta;
+    vj = vj * v;
+  }
+  lf.b[p.iQ()] = zh.neg();
+  lf.b_g = E.neg();
+  lf.a_wxi = Fr::one();
+  lf.a_wxiw = u;
+  lf.b[p.iWxi()] = xi;
+  lf.b[p.iWxiw()] = u * xi * w;
+  return lf;
+}
+
 // sum_t s_t * P_t over one segment (Straus: the terms share the doublings). Points are affine LEM on
 // the curve (or zero), scalars 32 B little-endian standard form, any 256-bit integer.
 inline G1 g1_lincomb_segment(const uint8_t* points_lem, const uint8_t* scalars_std, size_t nterms) {

@@ -300,6 +300,7 @@ struct Job {
                // 3 = one distributed proof over a rank group (proveGroup), 4 = msmPoints,
                // 5 = the multiplicities of a lookup table (lookupMultiplicities)
                // 6 = a batch of proofs against one ptau (verifyBatch)
+               // 7 = one proof of several arguments (proveMulti)
   int rc = 0;
   std::string err;
   // load
@@ -327,6 +328,14 @@ struct Job {
   std::vector<std::vector<uint8_t>> vb_bytes;
   std::vector<uint8_t> vb_valid;
   kgs_batch_diag_t vb_diag = {};
+  // proveMulti: the arguments' kinds and borrowed input views
+  struct MultiArg {
+    int kind = 0;
+    std::vector<View> f, t;
+    View sf, st;
+    bool selected = false;
+  };
+  std::vector<MultiArg> margs;
   // frOp
   int fr_op = 0;
   View in;
@@ -463,6 +472,34 @@ static void job_execute(napi_env, void* data) {
     const int rc = kgs_verify_batch_ptau(j->ctx, j->path.c_str(), j->vb_refs.data(), (int)j->vb_refs.size(),
                                          j->vb_valid.data(), &j->vb_diag);
     j->rc = rc < 0 ? rc : KGS_OK;
+  } else if (j->op == 7) {
+    const size_t E = (size_t)32 << j->nbits;
+    std::vector<kgs_arg_t> args(j->margs.size());
+    std::vector<kgs_arg_shape_t> shapes(j->margs.size());
+    std::vector<std::vector<const void*>> ptrs(2 * j->margs.size());
+    bool ok = true;
+    for (size_t a = 0; a < j->margs.size(); a++) {
+      const Job::MultiArg& m = j->margs[a];
+      for (size_t i = 0; i < m.f.size(); i++) {
+        ok &= m.f[i].p && m.t[i].p && m.f[i].len == E && m.t[i].len == E;
+        ptrs[2 * a].push_back(m.f[i].p);
+        ptrs[2 * a + 1].push_back(m.t[i].p);
+      }
+      if (m.selected) ok &= m.sf.p && m.st.p && m.sf.len == E && m.st.len == E;
+      args[a] = kgs_arg_t{m.kind, (int)m.f.size(), ptrs[2 * a].data(), ptrs[2 * a + 1].data(),
+                          m.selected ? m.sf.p : nullptr, m.selected ? m.st.p : nullptr};
+      shapes[a] = kgs_arg_shape_t{m.kind, (int)m.f.size(), m.selected ? 1 : 0};
+    }
+    if (!ok) {
+      j->rc = KGS_E_ARG;
+      j->err = "evaluation buffers must hold 2^nbits 32-byte elements";
+      return;
+    }
+    int nc = 1, ne = 1;  // shapes the library refuses are refused by kgs_prove_multi too, before it writes
+    kgs_multi_proof_shape(shapes.data(), (int)shapes.size(), &nc, &ne);
+    j->com.resize(64 * (size_t)nc);
+    j->ev.resize(32 * (size_t)ne);
+    j->rc = kgs_prove_multi(j->ctx, j->nbits, args.data(), (int)args.size(), j->com.data(), j->ev.data());
   } else if (j->op == 3) {
     if (prepare_prove(j)) group_execute(j);
     return;
@@ -665,6 +702,59 @@ static napi_value prove_args(napi_env env, napi_value* argv, size_t argc, Job* j
   return queue(env, j, j->op == 3 ? "kgs_prove_group" : "kgs_prove");
 }
 
+// proveMulti(ctx, nbits, [{kind, F: [..], T: [..], selF|null, selT|null}, ..])
+//   -> Promise<{commitments, evaluations}> in the order of kgs_prove_multi (include/kgs.h); the inputs are
+//   borrowed until the job completes and left as they are (no Montgomery write-back)
+static napi_value ProveMulti(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 7;
+  j->ctx = get_ctx(env, argv[0]);
+  napi_get_value_int32(env, argv[1], &j->nbits);
+  uint32_t m = 0;
+  napi_get_array_length(env, argv[2], &m);
+  bool ok = true;
+  for (uint32_t a = 0; a < m; a++) {
+    napi_value e, v, lf, lt;
+    napi_get_element(env, argv[2], a, &e);
+    Job::MultiArg ma;
+    napi_get_named_property(env, e, "kind", &v);
+    napi_get_value_int32(env, v, &ma.kind);
+    napi_get_named_property(env, e, "F", &lf);
+    napi_get_named_property(env, e, "T", &lt);
+    uint32_t nf = 0, nt = 0;
+    napi_get_array_length(env, lf, &nf);
+    napi_get_array_length(env, lt, &nt);
+    ok &= nf == nt;
+    for (uint32_t i = 0; i < nf && nf == nt; i++) {
+      napi_get_element(env, lf, i, &v);
+      ma.f.push_back(view_of(env, v, j->refs));
+      napi_get_element(env, lt, i, &v);
+      ma.t.push_back(view_of(env, v, j->refs));
+    }
+    napi_value sf, st;
+    napi_valuetype ty;
+    napi_get_named_property(env, e, "selF", &sf);
+    napi_get_named_property(env, e, "selT", &st);
+    napi_typeof(env, sf, &ty);
+    if (ty != napi_null && ty != napi_undefined) {
+      ma.selected = true;
+      ma.sf = view_of(env, sf, j->refs);
+      ma.st = view_of(env, st, j->refs);
+    }
+    j->margs.push_back(ma);
+  }
+  if (!ok || j->nbits < 1 || j->nbits > 28) {
+    for (napi_ref r : j->refs) napi_delete_reference(env, r);
+    delete j;
+    napi_throw_error(env, nullptr, "proveMulti: nbits in 1 .. 28 and, per argument, F and T lists of the same length");
+    return nullptr;
+  }
+  return queue(env, j, "kgs_prove_multi");
+}
+
 // frOp(ctx, op, Uint8Array) -> Promise<Uint8Array> on ctx's GPU, elementwise over 32 B elements:
 // op 0 = Fr.batchToMontgomery, 1 = Fr.batchFromMontgomery, 2 = Fr.batchInverse (0 -> 0),
 // 3 = Fr.fft, 4 = Fr.ifft (2^k elements, natural order) — the curve shim's batch members
@@ -823,6 +913,51 @@ static napi_value VerifyPtau(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// verifyMultiPtau(ptauPath, nbits, [{kind, npols, selected}, ..], commitments(Uint8Array), evaluations(Uint8Array))
+// -> boolean (host-only pairing check of a multi-argument proof, kgs_verify_multi_ptau)
+static napi_value VerifyMultiPtau(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  size_t plen = 0;
+  napi_get_value_string_utf8(env, argv[0], nullptr, 0, &plen);
+  std::string path(plen + 1, '\0');
+  napi_get_value_string_utf8(env, argv[0], &path[0], plen + 1, &plen);
+  path.resize(plen);
+  int32_t nbits = 0;
+  napi_get_value_int32(env, argv[1], &nbits);
+  uint32_t m = 0;
+  napi_get_array_length(env, argv[2], &m);
+  std::vector<kgs_arg_shape_t> shapes(m);
+  for (uint32_t a = 0; a < m; a++) {
+    napi_value e, v;
+    bool selected = false;
+    napi_get_element(env, argv[2], a, &e);
+    napi_get_named_property(env, e, "kind", &v);
+    napi_get_value_int32(env, v, &shapes[a].kind);
+    napi_get_named_property(env, e, "npols", &v);
+    napi_get_value_int32(env, v, &shapes[a].npols);
+    napi_get_named_property(env, e, "selected", &v);
+    napi_get_value_bool(env, v, &selected);
+    shapes[a].selected = selected ? 1 : 0;
+  }
+  std::vector<uint8_t> com = bytes_of(env, argv[3]), ev = bytes_of(env, argv[4]);
+  int nc = 0, ne = 0;
+  if (kgs_multi_proof_shape(shapes.data(), (int)m, &nc, &ne) != KGS_OK || com.size() != (size_t)nc * 64 ||
+      ev.size() != (size_t)ne * 32) {
+    napi_throw_error(env, nullptr, "proof buffers do not match the arguments' shapes");
+    return nullptr;
+  }
+  int rc = kgs_verify_multi_ptau(path.c_str(), nbits, shapes.data(), (int)m, com.data(), ev.data());
+  if (rc < 0) {
+    napi_throw_error(env, nullptr, "kgs_verify_multi_ptau failed");
+    return nullptr;
+  }
+  napi_value out;
+  napi_get_boolean(env, rc == 1, &out);
+  return out;
+}
+
 // groupCreateLocal(world) -> rank group of `world` contexts in this process (kgs_group_create_local):
 // the distributed prover with every vector sharded, driven from one Node process (one libuv
 // thread per rank). ctxSetGroup(ctx, group|null, rank) attaches / detaches a context.
@@ -958,6 +1093,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"frOp", nullptr, FrOp, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lookupMultiplicities", nullptr, LookupMultiplicities, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"verifyBatch", nullptr, VerifyBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"proveMulti", nullptr, ProveMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"verifyMultiPtau", nullptr, VerifyMultiPtau, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(desc) / sizeof(desc[0]), desc);
   return exports;

@@ -13,6 +13,9 @@ module.exports = {
     // the table's multiplicities from the witness and the table, and the prover that computes them itself
     lookup_multiplicities: require("./src/lookup/lookup_multiplicities"),
     lookup_kzg_grandsum_prover_from_table: require("./src/lookup/lookup_multiplicities").lookup_kzg_grandsum_prover_from_table,
+    // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
+    mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
+    mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),
     // many proofs against one ptau, one pairing check (kgs_verify_batch)
     kzg_verifier_batch: require("./src/verifier_batch"),
     // the provers' log channel (the reference's logger.js lines): setLogger(logplease instance), setLogLevel

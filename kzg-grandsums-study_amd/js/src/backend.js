@@ -132,6 +132,27 @@ function ptauPower(pTauFilename) {
     return load().ptauPower(path.resolve(pTauFilename));
 }
 
+// The SRS of `key` for domains up to 2^nBits on the slot's context. The load is an async job (a libuv
+// thread round trip) even when libkgs finds its tables already resident; it is skipped when this context
+// loaded the same file (same real path, size and mtime — the identity libkgs checks, so a rewritten ptau
+// is still re-read) for >= nBits (a file that cannot be stat'ed goes to libkgs, which reports it as the
+// drop-in always has)
+async function ensureSrs(slot, key, nBits) {
+    let id = null;
+    try {
+        const st = fs.statSync(key, { bigint: true });
+        id = `${fs.realpathSync(key)}#${st.size}#${st.mtimeNs}`;
+    } catch (e) {
+        id = null;
+    }
+    if (id === null || slot.srsId !== id || slot.srsBits < nBits) {
+        slot.srsId = null;
+        await load().srsLoadPtau(slot.ctx, key, nBits);
+        slot.srsId = id;
+        slot.srsBits = nBits;
+    }
+}
+
 // SRS load (only 2^(nBits+1) points, as prover.js:83-85 reads; grow-only device cache in libkgs)
 // and prove on the same held context: nothing can swap the SRS between the two
 async function prove(kind, pTauFilename, nBits, evalsF, evalsT, selF, selT) {
@@ -144,23 +165,7 @@ async function prove(kind, pTauFilename, nBits, evalsF, evalsT, selF, selT) {
     if (selT) selT = contiguous(selT);
     if (shardRanks() >= 2 && nBits >= shardMinBits()) return proveSharded(kind, key, nBits, evalsF, evalsT, selF, selT);
     return withContext(async slot => {
-        // the SRS load is an async job (a libuv thread round trip) even when libkgs finds its tables
-        // already resident; skip it when this context loaded the same file (same real path, size and
-        // mtime — the identity libkgs checks, so a rewritten ptau is still re-read) for >= nBits
-        // (a file that cannot be stat'ed goes to libkgs, which reports it as the drop-in always has)
-        let id = null;
-        try {
-            const st = fs.statSync(key, { bigint: true });
-            id = `${fs.realpathSync(key)}#${st.size}#${st.mtimeNs}`;
-        } catch (e) {
-            id = null;
-        }
-        if (id === null || slot.srsId !== id || slot.srsBits < nBits) {
-            slot.srsId = null;
-            await load().srsLoadPtau(slot.ctx, key, nBits);
-            slot.srsId = id;
-            slot.srsBits = nBits;
-        }
+        await ensureSrs(slot, key, nBits);
         setLanes(slot);
         const t0 = process.hrtime.bigint();
         const pending = load().prove(slot.ctx, kind, nBits, evalsF, evalsT, selF, selT);
@@ -175,6 +180,19 @@ async function prove(kind, pTauFilename, nBits, evalsF, evalsT, selF, selT) {
         diag.execMs = res.execMs;
         diag.timing = load().lastTiming(slot.ctx);
         return res;
+    });
+}
+
+// One proof of several arguments (kgs_prove_multi) on one held context; args: [{kind, F: [..], T: [..],
+// selF|null, selT|null}]. No Montgomery write-back, always one GPU (rank groups do not take it).
+async function proveMulti(pTauFilename, nBits, args) {
+    const key = path.resolve(pTauFilename);
+    args = args.map(a => ({ kind: a.kind, F: a.F.map(contiguous), T: a.T.map(contiguous),
+                            selF: a.selF ? contiguous(a.selF) : null, selT: a.selT ? contiguous(a.selT) : null }));
+    return withContext(async slot => {
+        await ensureSrs(slot, key, nBits);
+        setLanes(slot);
+        return load().proveMulti(slot.ctx, nBits, args);
     });
 }
 
@@ -230,4 +248,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };

@@ -8,11 +8,9 @@ const { getCurveFromName } = require("./curve");
 
 const TITLE = ["GRAND-SUM", "GRAND-PRODUCT", "GRAND-SUM (LOOKUP)"];
 
-async function prove(kind, pTauFilename, evalsFs, evalsTs, evalsSelF, evalsSelT) {
-    logger.info(`> MULTISET EQUALITY KZG ${TITLE[kind]} PROVER STARTED`);
-    // the ptau header is read first, as the reference does (prover.js:15-16)
-    const nBitsPTau = backend.ptauPower(pTauFilename);
-    const curve = await getCurveFromName("bn128");
+// The reference's input checks (prover.js:22-81), same messages; shared with the multi-argument prover,
+// which runs them per argument. Returns the lists, the selectors (materialised when selected) and nBits.
+function checkInputs(kind, nBitsPTau, curve, evalsFs, evalsTs, evalsSelF, evalsSelT) {
     if (!Array.isArray(evalsFs)) evalsFs = [evalsFs];
     if (!Array.isArray(evalsTs)) evalsTs = [evalsTs];
     if (evalsFs.length !== evalsTs.length) throw new Error(`The lengths of the two vector multisets must be the same.`);
@@ -52,6 +50,17 @@ async function prove(kind, pTauFilename, evalsFs, evalsTs, evalsSelF, evalsSelT)
     const nBits = Math.ceil(Math.log2(evalsFs[0].length()));
     if (evalsFs[0].length() !== 2 ** nBits) throw new Error("Polynomial length must be a power of two.");
     if (nBitsPTau < nBits) throw new Error("The Powers of Tau file is not sufficiently large to commit the polynomials.");
+    return { evalsFs, evalsTs, evalsSelF, evalsSelT, nPols, isSelected, nBits };
+}
+
+async function prove(kind, pTauFilename, evalsFs, evalsTs, evalsSelF, evalsSelT) {
+    logger.info(`> MULTISET EQUALITY KZG ${TITLE[kind]} PROVER STARTED`);
+    // the ptau header is read first, as the reference does (prover.js:15-16)
+    const nBitsPTau = backend.ptauPower(pTauFilename);
+    const curve = await getCurveFromName("bn128");
+    const checked = checkInputs(kind, nBitsPTau, curve, evalsFs, evalsTs, evalsSelF, evalsSelT);
+    ({ evalsFs, evalsTs, evalsSelF, evalsSelT } = checked);
+    const { nPols, isSelected, nBits } = checked;
 
     const logInfo = logger.enabled("INFO");
     if (logInfo) {  // prover.js:87-93
@@ -218,4 +227,4 @@ function logRounds(kind, curve, proof, nBits, nPols, isSelected) {
     return { beta, gamma, alpha, xi, v };
 }
 
-module.exports = { prove, Transcript, logRounds };
+module.exports = { prove, checkInputs, Transcript, logRounds };
