@@ -1,6 +1,8 @@
 // Internal interface of the prover library (not part of the C-ABI): the context, the shared
-// device tables and the host-side building blocks of a proof. Shared by prover.cpp (single-GPU
-// prover, C-ABI) and prover_dist.cpp (the distributed prover over a rank group).
+// device tables and the host-side building blocks of a proof. Shared by prover.cpp (building blocks,
+// single prover, C-ABI), prover_rounds.cpp (the protocol rounds of the single and the multi-argument
+// prover), prover_multi.cpp (the multi prover's entry points) and prover_dist.cpp (the
+// distributed prover over a rank group).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -416,6 +418,7 @@ struct Commit {
   uint8_t* h_T2 = nullptr;  // second point range's partial (commit_launch_split), or nullptr
 };
 void shard_range(uint64_t n, int rank, int world, uint64_t& lo, uint64_t& hi);
+hipStream_t copy_stream();  // a new stream for the host-boundary copies (st_copy, st_wb)
 void fork_lanes(kgs_ctx& c);
 // work issued on `to` after this waits for everything issued on `from` so far
 void lane_join(kgs_ctx& c, hipStream_t from, hipStream_t to);
@@ -465,19 +468,95 @@ struct LcTerms {
 };
 void run_lincomb(hipStream_t st, uint32_t* out, uint64_t n, const LcTerms& t);
 
-struct ProveIn {
+// ------------------------------------------------------------------ the protocol rounds (prover_rounds.cpp)
+enum R5Poly { R5_S, R5_Q, R5_F, R5_T, R5_SELF, R5_SELT, R5_POLT };
+
+// One argument of a proof. The shape arithmetic of the protocol lives here and nowhere else.
+struct ArgIn {
+  int kind = 0, k = 0;
+  std::vector<const uint32_t*> f_std, t_std;          // device, standard form
+  const uint32_t *sel_f = nullptr, *sel_t = nullptr;  // device, Montgomery (nullptr: unselected)
+  bool gs() const { return kind != KGS_GRANDPRODUCT; }  // KGS_LOOKUP is a selected grand-sum
+  bool lk() const { return kind == KGS_LOOKUP; }
+  bool sel() const { return sel_f != nullptr; }
+  int ncom_r1() const { return 2 * k + (sel() ? 2 : 0); }                  // round-1 commitments
+  int nev_xi() const { return (gs() ? 2 : 1) * k + (sel() ? 2 : 0); }      // openings at xi
+  // fn(R5Poly, index) for every polynomial opened at xi. Proof (and transcript) order interleaves
+  // F_0 [T_0] F_1 [T_1] ...; the powers of v in W_xi run over every F_i, then every T_i. A grand
+  // product does not open its T_i. The selectors come last in both.
+  template <class Fn>
+  void each_xi(bool by_power, Fn fn) const {
+    for (int i = 0; i < k; i++) {
+      fn(R5_F, i);
+      if (gs() && !by_power) fn(R5_T, i);
+    }
+    for (int i = 0; i < k && gs() && by_power; i++) fn(R5_T, i);
+    if (sel()) {
+      fn(R5_SELF, 0);
+      fn(R5_SELT, 0);
+    }
+  }
+};
+
+// an argument's polynomials in coefficient form (device), as round 5 names them
+struct ArgPolys {
+  std::vector<uint32_t*> Fc, Tc;
+  uint32_t *sFc = nullptr, *sTc = nullptr, *Sc = nullptr;
+  const uint32_t *polT = nullptr, *Qc = nullptr;
+  const uint32_t* poly(R5Poly id, int idx) const {
+    switch (id) {
+      case R5_S: return Sc;
+      case R5_Q: return Qc;
+      case R5_F: return Fc[idx];
+      case R5_T: return Tc[idx];
+      case R5_SELF: return sFc;
+      case R5_SELT: return sTc;
+      case R5_POLT: return polT;
+    }
+    return nullptr;
+  }
+};
+
+// an argument's round-4 values at xi; unpack() takes them in proof order (ArgIn::each_xi)
+struct XiEvals {
+  std::vector<Fr> fx, tx;
+  Fr sFx = Fr::zero(), sTx = Fr::zero();
+  Fr& at(R5Poly id, int idx) { return id == R5_F ? fx[idx] : id == R5_T ? tx[idx] : id == R5_SELF ? sFx : sTx; }
+  const Fr* unpack(const ArgIn& a, const Fr* ev) {
+    fx.assign(a.k, Fr::zero());
+    tx.assign(a.k, Fr::zero());
+    a.each_xi(false, [&](R5Poly id, int i) { at(id, i) = *ev++; });
+    return ev;
+  }
+};
+
+// The host-boundary hooks of kgs_prove (all empty for device-resident inputs). Input vectors are numbered
+// F_i at 2i, T_i at 2i + 1, then selF, selT.
+struct HostHooks {
+  std::vector<uint8_t*> mont_f_out, mont_t_out;  // host outputs (may be empty)
+  std::function<void()> after_round1;             // called once round 1 is synchronised (write-back on st_wb)
+  // per input vector an event the vector's first kernel waits for, or nullptr (already ordered on the
+  // main stream)
+  std::vector<hipEvent_t> ready;
+  // blocks until vector v's DMA (and ready[v]) has been enqueued; null: all already are
+  std::function<void(size_t)> input_issued;
+};
+struct ProveIn : HostHooks {
   int kind, nbits, npols;
   std::vector<const uint32_t*> f_std, t_std;  // device, standard form
   const uint32_t *sel_f = nullptr, *sel_t = nullptr;  // device, Montgomery (nullptr: unselected)
-  std::vector<uint8_t*> mont_f_out, mont_t_out;  // host outputs (may be empty)
-  std::function<void()> after_round1;             // called once round 1 is synchronised (write-back on st_wb)
-  // kgs_prove: per input vector (F_i at 2i, T_i at 2i + 1, then selF, selT) an event the main stream
-  // waits for before the vector's first kernel, or nullptr (already ordered on the main stream)
-  std::vector<hipEvent_t> ready;
-  // kgs_prove: blocks until vector v's DMA (and ready[v]) has been enqueued; null: all already are
-  std::function<void(size_t)> input_issued;
+  ArgIn arg() const {
+    ArgIn a;
+    a.kind = kind;
+    a.k = npols;
+    a.f_std = f_std;
+    a.t_std = t_std;
+    a.sel_f = sel_f;
+    a.sel_t = sel_t;
+    return a;
+  }
 };
-enum R5Poly { R5_S, R5_Q, R5_F, R5_T, R5_SELF, R5_SELT, R5_POLT };
+
 struct R5Term {
   R5Poly id;
   int idx;  // vector index for R5_F / R5_T
@@ -491,6 +570,67 @@ R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& 
                 const Fr& xi, const std::vector<Fr>& fx, const std::vector<Fr>& tx, const Fr& sFx, const Fr& sTx,
                 const Fr& sxiw, bool lookup, const Fr* fxi_override = nullptr);
 
+// What distinguishes the callers of prove_rounds. The engine never infers these from the argument count.
+struct RoundOpts {
+  const HostHooks* hooks = nullptr;
+  // round 1: each input vector's conversion, transform and commitment on the lane of its commitment
+  // (else: every transform on the main stream, then the commitments alternate between the lanes)
+  bool piped_round1 = false;
+  // follow the reference on degenerate inputs (ref_quirks.cpp); one argument only
+  bool ref_quirks = false;
+  // "argument j: " in front of NOT_WELL_CALC and NOT_DIVISIBLE
+  bool name_arguments = false;
+};
+// Rounds 1 to 5 of a proof of m >= 1 arguments over one domain. Commitments and
+// evaluations in proof order; ends synchronised. The caller has checked the shapes and the SRS
+// (check_srs) and holds the context.
+void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const RoundOpts& o, uint8_t* com_out,
+                  uint8_t* ev_out);
+// the SRS preconditions every prover shares word for word
+void check_srs(const kgs_ctx& c, int nbits);
+std::string arg_prefix(int j);  // "argument j: "
+
+// the per-round wall clock (kgs_last_timing) and roctx range of a proof
+struct RoundClock {
+  kgs_ctx& c;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  Range range{ROUND_NAMES[0]};
+  explicit RoundClock(kgs_ctx& ctx) : c(ctx) {}
+  void lap(int r) {
+    const auto t1 = std::chrono::steady_clock::now();
+    c.timing[r] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+    if (r + 1 < 5) range.push(ROUND_NAMES[r + 1]);
+    else range.pop();
+  }
+};
+
+// in-flight contexts (one MSM lane) launch the NTT passes built to co-reside with the other proofs'
+// accumulate waves, the latency mode (two lanes) the build that is fastest alone (ntt.hip, WV)
+struct NttMode {
+  bool prev;
+  explicit NttMode(bool on) : prev(ntt_set_coresident(on)) {}
+  ~NttMode() { ntt_set_coresident(prev); }
+};
+
+// The provers' error contract: a call that leaves by an exception drains every stream of the context
+// first, so nothing of it still reads the caller's buffers. Rank-group contexts are left alone: their
+// main stream may wait in an exchange whose peers failed (the group's abort releases it), and they
+// never DMA caller memory in place.
+struct DrainOnError {
+  kgs_ctx* ctx;
+  int unwinding = std::uncaught_exceptions();
+  explicit DrainOnError(kgs_ctx* c) : ctx(c) {}
+  ~DrainOnError() {
+    if (std::uncaught_exceptions() <= unwinding || ctx->group) return;
+    hipSetDevice(ctx->device);
+    for (hipStream_t s : {ctx->st, ctx->st2, ctx->st_copy, ctx->st_wb})
+      if (s) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+  }
+};
+
+// the single-argument prover (prover.cpp): its checks, the rank-group dispatch, then prove_rounds
 void prove_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out);
 // the distributed prover (prover_dist.cpp): same inputs and outputs as prove_impl on every rank
 void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out);

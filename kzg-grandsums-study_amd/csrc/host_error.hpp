@@ -21,3 +21,18 @@ inline int kgs_fail(const KgsError& e) {
 }
 
 }  // namespace kgs
+
+// The error boundary of a C-ABI entry point whose failures are the device's (KGS_E_HIP for anything that
+// is not a KgsError): `API_BEGIN body API_END` returns KGS_OK unless the body returns or throws. The codes
+// come from include/kgs.h at the place of use.
+#define API_BEGIN try {
+#define API_END                     \
+  }                                 \
+  catch (const KgsError& e) {       \
+    return kgs_fail(e);             \
+  }                                 \
+  catch (const std::exception& e) { \
+    kgs_errbuf() = e.what();        \
+    return KGS_E_HIP;               \
+  }                                 \
+  return KGS_OK;

@@ -101,7 +101,7 @@ void launch_builder(hipStream_t st, bool prod, bool sel, uint32_t* out, const ui
 void launch_quotient(hipStream_t st, bool prod, bool sel, uint32_t* q, const uint32_t* S, const uint32_t* F,
                      const uint32_t* T, const uint32_t* SF, const uint32_t* ST, const uint32_t* inv_nxm1,
                      const uint32_t* scalars, int lcs, uint32_t rot);
-// The quotient of a multi-argument proof (prover_multi.cpp): up to QM_MAX arguments per launch share the
+// The quotient of a multi-argument proof (prover_rounds.cpp): up to QM_MAX arguments per launch share the
 // coset point, the Z_H and L1 factors and the store. Argument j contributes delta^j times its numerator.
 constexpr int QM_MAX = 8;
 struct QuotArg {

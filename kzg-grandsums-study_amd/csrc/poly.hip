@@ -429,7 +429,7 @@ void launch_quotient(hipStream_t st, bool prod, bool sel, uint32_t* q, const uin
 #undef KGS_Q
 }
 
-// Multi-argument quotient (prover_multi.cpp): Q = (sum_j delta^j N_j) / Z_H for up to QM_MAX arguments per
+// Multi-argument quotient (prover_rounds.cpp): Q = (sum_j delta^j N_j) / Z_H for up to QM_MAX arguments per
 // launch, each with its own kind and selectors. Per coset point the arguments' cores and L1 operands are
 // weighted by delta^j (29-bit products, lazy sums on [0, 2p)) and summed in registers; alpha / Z_H and
 // 1/(n(x - 1)) multiply the two sums once and q is stored once. The descriptor comes by value (kernarg),

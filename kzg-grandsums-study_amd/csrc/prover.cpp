@@ -671,6 +671,9 @@ R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& 
   return r;
 }
 
+// The single-argument prover: its own checks, the rank-group dispatch, then the rounds (prover_rounds.cpp)
+// with what is special about it — kgs_prove's host-boundary hooks, round 1 piped over the two lanes when
+// commitments are split, and the reference's behaviour on degenerate inputs (never for a lookup).
 void prove_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out) {
   if (in.kind != KGS_GRANDSUM && in.kind != KGS_GRANDPRODUCT && in.kind != KGS_LOOKUP)
     throw KgsError(KGS_E_ARG, "unknown argument kind");
@@ -682,458 +685,17 @@ void prove_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out
     prove_dist_group(c, in, com_out, ev_out);
     return;
   }
-  // in-flight contexts (one MSM lane) launch the NTT passes built to co-reside with the other proofs'
-  // accumulate waves, the latency mode (two lanes) the build that is fastest alone (ntt.hip, WV)
-  struct NttMode {
-    bool prev;
-    explicit NttMode(bool on) : prev(ntt_set_coresident(on)) {}
-    ~NttMode() { ntt_set_coresident(prev); }
-  } ntt_mode(c.msm_lanes < 2);
-  using clk = std::chrono::steady_clock;
-  auto t0 = clk::now();
-  // every slot, the host-boundary ones [6..8] too: kgs_prove writes them after this returns, and a
-  // device-resident proof must not report a previous host call's copy and prover times
-  c.timing.assign(9, 0.0);
-  Range range(ROUND_NAMES[0]);
-  auto lap = [&](int r) {
-    auto t1 = clk::now();
-    c.timing[r] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    if (r + 1 < 5) range.push(ROUND_NAMES[r + 1]);
-    else range.pop();
-  };
-  const bool gs = in.kind != KGS_GRANDPRODUCT;  // KGS_LOOKUP is a selected grand-sum
-  const bool lk = in.kind == KGS_LOOKUP;
-  const bool sel = in.sel_f != nullptr;
-  const int k = in.npols;
-  const int nbits = in.nbits;
-  const uint64_t n = 1ull << nbits;
-  const size_t E = 32 * n;
-  if (nbits < 1) throw KgsError(KGS_E_ARG, "nbits must be >= 1");
-  if (c.srs_power < 0) throw KgsError(KGS_E_ARG, "no SRS loaded");
-  if (c.srs_slice_world > 1)
-    throw KgsError(KGS_E_ARG, "this context holds a rank's SRS slice: it proves only as that rank of a group (kgs_ctx_set_group)");
-  if (c.srs_power < nbits)
-    throw KgsError(KGS_E_SRS, "The Powers of Tau file is not sufficiently large to commit the polynomials.");
-  if (nbits > c.nbits_max) throw KgsError(KGS_E_SRS, "SRS loaded for a smaller maximum domain; reload with larger nbits_max");
-  if (k < 1) throw KgsError(KGS_E_ARG, "The number of multisets must be greater than 0.");
-  if (k > KGS_MAX_POLS) throw KgsError(KGS_E_ARG, "too many multisets");
-  // pinned staging for this proof's host round trips: commit partials (c x 128 B each), the
-  // round-4 Horner tile partials (32 B per 2048 coefficients per evaluated polynomial), flags and
-  // scalars (each bump allocation rounds up to 64 B)
-  const int ncom_all = 2 * k + (in.sel_f ? 2 : 0) + 4;
-  c.msm_slots = ncom_all + 4;
-  {
-    const size_t ntl = (size_t)((n + EVAL_TILE - 1) / EVAL_TILE);
-    const size_t need = (size_t)(ncom_all + 4) * ((size_t)c.tb.c * 128 + 64) + 32 * ntl * (2 * k + 3) + 64 * 8 +
-                        ((size_t)kgs_ctx::SCAL_BYTES * 2) + (1 << 20);
-    c.ensure_pin(need > ((size_t)8 << 20) ? need : ((size_t)8 << 20));
-  }
-  c.reset_staging();
-  uint32_t* flags = c.buf("flags", 64);
-  HC(hipMemsetAsync(flags, 0, 64, c.st));
-  const bool vec = k > 1;
-
-  // ---------------- round 1: witness polynomials + commitments (prover.js:144-179)
-  std::vector<uint32_t*> fm(k), tm(k), Fc(k), Tc(k);
-  for (int i = 0; i < k; i++) {
-    fm[i] = c.buf("fm" + std::to_string(i), E);
-    tm[i] = c.buf("tm" + std::to_string(i), E);
-    Fc[i] = c.buf("Fc" + std::to_string(i), E);
-    Tc[i] = c.buf("Tc" + std::to_string(i), E);
-  }
-  uint32_t *sFc = nullptr, *sTc = nullptr;
-  if (sel) {
-    sFc = c.buf("sFc", E);
-    sTc = c.buf("sTc", E);
-  }
-  // Host-buffer inputs (kgs_prove) arrive vector by vector: in.input_issued(v) returns once vector
-  // v's DMA is enqueued (its host copy may still be running on another thread before that), and
-  // in.ready[v] is the event its first kernel waits for.
-  auto wait_input = [&](size_t v, hipStream_t st) {
-    if (in.input_issued) in.input_issued(v);
-    if (v < in.ready.size() && in.ready[v]) HC(hipStreamWaitEvent(st, in.ready[v], 0));
-  };
-  // Montgomery write-back (prover.js:147-148): vector v's D2H on the write-back stream right after
-  // its conversion on `st` (not after the round's MSMs, and never queued between input DMAs)
-  int nwb = 0;
-  auto write_back = [&](uint8_t* dst, const uint32_t* src, hipStream_t st) {
-    if (!dst) return;
-    if (!c.st_wb) c.st_wb = copy_stream();
-    if ((int)c.ev_wb.size() <= nwb) {
-      hipEvent_t e;
-      HC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c.ev_wb.push_back(e);
-    }
-    HC(hipEventRecord(c.ev_wb[nwb], st));
-    HC(hipStreamWaitEvent(c.st_wb, c.ev_wb[nwb], 0));
-    nwb++;
-    // hipMemcpyAsync. Into pinned memory the runtime runs it as its copyBuffer shader kernel, not on an
-    // SDMA engine: ~0.8 ms of CU residency per 32 MiB in flight; hipMemcpyDtoHAsync does the same
-    // (profiles/r06/host_engine/, wb_api/). KGS_WB_COPY=kernel stores from our own shader into the
-    // mapped pinned buffer instead (poly.hip k_host_store): measured slower in flight, 83-85 vs 86-88
-    // proofs/s (profiles/r05/wb_ab.txt), kept for A/B
-    static const unsigned wb_blocks = [] {
-      const char* e = getenv("KGS_WB_COPY");
-      if (!(e && !strcmp(e, "kernel"))) return 0u;
-      const char* b = getenv("KGS_WB_BLOCKS");
-      return b ? (unsigned)atoi(b) : 64u;
-    }();
-    void* mapped = nullptr;
-    if (wb_blocks && hipHostGetDevicePointer(&mapped, dst, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      mapped = nullptr;
-    }
-    if (mapped && E % 16 == 0) launch_host_store(c.st_wb, mapped, src, E, wb_blocks);
-    else HC(hipMemcpyAsync(dst, src, E, hipMemcpyDeviceToHost, c.st_wb));
-  };
-  auto mont_out = [&](const std::vector<uint8_t*>& v, int i) -> uint8_t* { return v.empty() ? nullptr : v[i]; };
-  std::vector<Commit> r1;
-  int slot = 0;
-  // With two MSM lanes (a proof alone on its context: the latency mode) each input vector's whole
-  // round-1 chain — Montgomery conversion, iNTT, commitment MSM — runs on the lane of its
-  // commitment, F_i / selF on lane 0 and T_i / selT on lane 1, so that T's transfer (host buffers)
-  // and T's transform overlap F's MSM instead of delaying it.
-  const bool piped = split_commits(c);
-  if (piped) {
-    fork_lanes(c);
-    for (int i = 0; i < k; i++) {
-      wait_input(2 * i, c.st);
-      launch_to_mont(c.st, fm[i], in.f_std[i], n);
-      write_back(mont_out(in.mont_f_out, i), fm[i], c.st);
-      intt_nat(c, Fc[i], fm[i], nbits);
-      r1.push_back(commit_launch(c, Fc[i], n, slot++, 0));
-      wait_input(2 * i + 1, c.st2);
-      launch_to_mont(c.st2, tm[i], in.t_std[i], n);
-      write_back(mont_out(in.mont_t_out, i), tm[i], c.st2);
-      intt_nat(c, Tc[i], tm[i], nbits, c.st2);
-      r1.push_back(commit_launch(c, Tc[i], n, slot++, 1));
-    }
-    check_launch();
-  } else {
-    for (int i = 0; i < k; i++) {
-      wait_input(2 * i, c.st);
-      launch_to_mont(c.st, fm[i], in.f_std[i], n);
-      write_back(mont_out(in.mont_f_out, i), fm[i], c.st);
-      wait_input(2 * i + 1, c.st);
-      launch_to_mont(c.st, tm[i], in.t_std[i], n);
-      write_back(mont_out(in.mont_t_out, i), tm[i], c.st);
-      intt_nat(c, Fc[i], fm[i], nbits);
-      intt_nat(c, Tc[i], tm[i], nbits);
-    }
-    check_launch();
-  }
-  // fm/tm are not written again before the round-1 sync (the write-back reads them on st_wb)
-  if (sel) {
-    if (piped) {
-      wait_input(2 * k, c.st);
-      intt_nat(c, sFc, in.sel_f, nbits);
-      r1.push_back(commit_launch(c, sFc, n, slot++, 0));
-      wait_input(2 * k + 1, c.st2);
-      intt_nat(c, sTc, in.sel_t, nbits, c.st2);
-      r1.push_back(commit_launch(c, sTc, n, slot++, 1));
-    } else {
-      wait_input(2 * k, c.st);
-      intt_nat(c, sFc, in.sel_f, nbits);
-      wait_input(2 * k + 1, c.st);
-      intt_nat(c, sTc, in.sel_t, nbits);
-    }
-  }
-  if (!piped) {
-    fork_lanes(c);
-    for (int i = 0; i < k; i++) {
-      r1.push_back(commit_launch(c, Fc[i], n, slot++, 0));
-      r1.push_back(commit_launch(c, Tc[i], n, slot++, 1));
-    }
-    if (sel) {
-      r1.push_back(commit_launch(c, sFc, n, slot++, 0));
-      r1.push_back(commit_launch(c, sTc, n, slot++, 1));
-    }
-  }
-  // round 1's commitments only: the Montgomery write-back on st_wb keeps running under rounds 2-5
-  // (in.after_round1's thread waits for it before copying to the caller)
-  HC(hipStreamSynchronize(c.st));
-  if (c.st2) HC(hipStreamSynchronize(c.st2));
-  if (in.after_round1) in.after_round1();
-  const int ncom = 2 * k + (sel ? 2 : 0) + 4;
-  std::vector<std::vector<uint8_t>> com(ncom, std::vector<uint8_t>(64));
-  int ci = 0;
-  {
-    std::vector<uint8_t*> outs;
-    for (size_t i = 0; i < r1.size(); i++) outs.push_back(com[ci++].data());
-    commits_finish(c, r1, outs);
-  }
-  lap(0);
-
-  // ---------------- round 2: challenges, combined polynomials, S / Z (prover.js:181-231)
-  host::Transcript tr;
-  for (int i = 0; i < ci; i++) tr.add_commitment(com[i].data());
-  Fr beta = Fr::zero();
-  if (vec) {
-    beta = tr.challenge();
-    tr.add_scalar(beta);
-  }
-  const Fr gamma = tr.challenge();
-  std::vector<Fr> bpow(k);
-  bpow[0] = Fr::one();
-  for (int i = 1; i < k; i++) bpow[i] = bpow[i - 1] * beta;
-  // Two lanes (latency mode): the challenge-independent coset evaluations of F, T (+ selectors) run on
-  // lane 1 from the start of the round, beside the builder's serial part (k_tile_inverse is one
-  // workgroup) and S's inverse NTT on lane 0; S's commitment follows on lane 0, S's coset evaluation
-  // on lane 1 once S exists. One lane: the same work in order on the main stream.
-  fork_lanes(c);
-  hipStream_t s2 = c.msm_lanes >= 2 && c.st2 ? c.st2 : c.st;
-  const int lcs = (!gs && !sel) ? nbits : nbits + 1;
-  const uint64_t cs = 1ull << lcs;
-  uint32_t* cosS = c.buf("cosS", 32 * cs);
-  uint32_t* cosF = c.buf("cosF", 32 * cs);
-  uint32_t* cosT = c.buf("cosT", 32 * cs);
-  uint32_t *cosSF = nullptr, *cosST = nullptr;
-  const uint32_t *fcomb = fm[0], *tcomb = tm[0], *polF = Fc[0], *polT = Tc[0];
-  if (vec) {
-    uint32_t* b_fe = c.buf("fcomb", E);
-    uint32_t* b_te = c.buf("tcomb", E);
-    uint32_t* b_F = c.buf("polF", E);
-    uint32_t* b_T = c.buf("polT", E);
-    LcTerms l1, l2, l3, l4;
-    for (int i = 0; i < k; i++) {
-      l1.add(fm[i], n, bpow[i]);
-      l2.add(tm[i], n, bpow[i]);
-      l3.add(Fc[i], n, bpow[i]);
-      l4.add(Tc[i], n, bpow[i]);
-    }
-    run_lincomb(c.st, b_fe, n, l1);
-    run_lincomb(c.st, b_te, n, l2);
-    run_lincomb(s2, b_F, n, l3);
-    run_lincomb(s2, b_T, n, l4);
-    fcomb = b_fe;
-    tcomb = b_te;
-    polF = b_F;
-    polT = b_T;
-  }
-  coset_fwd(c, cosF, polF, n, lcs, s2);
-  coset_fwd(c, cosT, polT, n, lcs, s2);
-  if (sel) {
-    cosSF = c.buf("cosSF", 32 * cs);
-    cosST = c.buf("cosST", 32 * cs);
-    coset_fwd(c, cosSF, sFc, n, lcs, s2);
-    coset_fwd(c, cosST, sTc, n, lcs, s2);
-  }
-  uint32_t* Sev = c.buf("Sev", E);
-  uint32_t* Sc = c.buf("Sc", E);
-  const uint32_t ntiles = (uint32_t)((n + EVAL_TILE - 1) / EVAL_TILE);
-  uint32_t* d_gamma = c.scal(&gamma, 1);
-  launch_builder(c.st, !gs, sel, Sev, fcomb, tcomb, in.sel_f, in.sel_t, d_gamma, n, c.buf("bt_tp", 32 * (ntiles + 1)),
-                 c.buf("bt_ti", 32 * (ntiles + 1)), flags);
-  intt_nat(c, Sc, Sev, nbits);
-  check_launch();
-  lane_join(c, c.st, s2);
-  coset_fwd(c, cosS, Sc, n, lcs, s2);
-  Commit cS = commit_launch(c, Sc, n, slot++, 0);
-  uint32_t* nxm1 = get_nxm1(c, nbits, lcs);
-  check_launch();
-  uint32_t* h_flags = (uint32_t*)c.pin(64);
-  HC(hipMemcpyAsync(h_flags, flags, 64, hipMemcpyDeviceToHost, c.st));
-  c.sync();
-  if (h_flags[0])
-    throw KgsError(KGS_E_NOT_WELL_CALC, gs ? "The grand-sum polynomial S is not well calculated"
-                                             : "The grand-product polynomial Z is not well calculated");
-  const int iS = ci;
-  commit_finish(c, cS, com[ci++].data());
-  lap(1);
-
-  // ---------------- round 3: quotient on a coset (prover.js:233-286)
-  tr.add_scalar(gamma);
-  tr.add_commitment(com[iS].data());
-  const Fr alpha = tr.challenge();
-  const uint32_t rot = (uint32_t)(cs >> nbits);
-  uint64_t qlen = (!gs && !sel) ? n - 1 : 2 * n - 2;  // deg Q + 1 bound
-  Fr gn = Fr::from_u64(5).pow_u64(n);
-  // alpha_t: weight of the selT-binary term (none for a lookup, whose selT holds multiplicities)
-  // 1/Z_H on the two coset halves, times 1/cs (the scaling of the inverse transform below; nxm1 carries it too)
-  const Fr inv_cs = Fr::from_u64(cs).inverse();
-  Fr qs[9] = {alpha, gamma, (gn - Fr::one()).inverse() * inv_cs, (gn.neg() - Fr::one()).inverse() * inv_cs,
-              lk ? Fr::zero() : alpha};
-  // k_quotient: alpha / Z_H on each coset half as one 29-bit product record (slots 5-6, 7-8)
-  fr29_record(alpha * qs[2], qs + 5);
-  fr29_record(alpha * qs[3], qs + 7);
-  uint32_t* d_qs = c.scal(qs, 9);
-  launch_divcheck(c.st, !gs, sel, flags + 1, Sev, fcomb, tcomb, in.sel_f, in.sel_t, d_qs, n);
-  const uint32_t* Qc = c.buf("Qc", 32 * cs);
-  launch_quotient(c.st, !gs, sel, (uint32_t*)Qc, cosS, cosF, cosT, cosSF, cosST, nxm1, d_qs, lcs, rot);
-  coset_inv_prescaled(c, (uint32_t*)Qc, Qc, lcs);
-  check_launch();
-  // latency mode: Q's 2n points over both MSM lanes (one lane's sort and tail overlap the other's
-  // accumulation)
-  fork_lanes(c);
-  Commit cQ = commit_launch_split(c, Qc, qlen, qlen / 2, slot);
-  slot += 2;
-  std::vector<const uint32_t*> qops = {polF, polT, Sc};
-  if (sel) {
-    qops.push_back(sFc);
-    qops.push_back(sTc);
-  }
-  const uint32_t* probe = c.ref_quirks && !lk ? ref_quirks_probe(c, n, qops, Qc, qlen) : nullptr;
-  HC(hipMemcpyAsync(h_flags, flags, 64, hipMemcpyDeviceToHost, c.st));
-  c.sync();
-  // Reference-quirks mode (ref_quirks.cpp): where the reference's own quotient chain does not compute
-  // the quotient (an operand of degree 1 <= d < n/2) it is replayed with the reference's buffer
-  // semantics and its Q replaces ours; otherwise the only difference is the reference's RangeError
-  // on a zero quotient (divZh, after its divisibility check).
-  const uint32_t* Fmut = nullptr;  // polF's buffer after the replay wrote into it (Q2), else nullptr
-  bool replayed = false;
-  if (probe) {
-    if (ref_quirks_needed(probe, qops.size(), n)) {
-      uint32_t* fm_out = nullptr;
-      Qc = ref_quirks_quotient(c, gs, sel, lk, nbits, alpha, gamma, polF, polT, Sc, sFc, sTc, qlen, fm_out);
-      Fmut = fm_out;
-      replayed = true;
-      // multiExponentiation reads degree()+1 points of the reference's 2n-point PTau buffer
-      // (prover.js:83-84, polynomial.js:1106-1110); past it, ffjavascript's multiExpAffine gets fewer
-      // bases than scalars, which is not reproduced
-      if (qlen > 2 * n)
-        throw KgsError(KGS_E_ARG, "reference-quirks mode: the reference's Q has more coefficients than its 2n-point SRS buffer");
-      cQ = commit_launch_split(c, Qc, qlen, qlen / 2, slot);
-      slot += 2;
-      c.sync();
-    }
-  }
-  if (!replayed) {
-    if (h_flags[1]) throw KgsError(KGS_E_NOT_DIVISIBLE, "Polynomial is not divisible");
-    if (probe && ref_quotient_is_zero(probe)) throw KgsError(KGS_E_RANGE, "offset is out of bounds");
-  }
-  const int iQ = ci;
-  commit_finish(c, cQ, com[ci++].data());
-  lap(2);
-
-  // ---------------- round 4: evaluations (prover.js:288-318)
-  tr.add_scalar(alpha);
-  tr.add_commitment(com[iQ].data());
-  const Fr xi = tr.challenge();
-  const Fr w = fr_w(nbits);
-  const Fr xiw = xi * w;
-  std::vector<const uint32_t*> esrc;
-  std::vector<uint64_t> elen;
-  // reference-quirks mode, polF's buffer shared and rewritten (Q2): the reference's later reads of polF
-  // see the new values — polFs[0] itself for one multiset, only polF.evaluate (prover.js:360) for vectors
-  if (Fmut && !vec) Fc[0] = (uint32_t*)Fmut;
-  for (int i = 0; i < k; i++) {
-    esrc.push_back(Fc[i]);
-    elen.push_back(n);
-    if (gs) {
-      esrc.push_back(Tc[i]);
-      elen.push_back(n);
-    }
-  }
-  if (sel) {
-    esrc.push_back(sFc);
-    elen.push_back(n);
-    esrc.push_back(sTc);
-    elen.push_back(n);
-  }
-  if (Fmut && vec) {
-    esrc.push_back(Fmut);
-    elen.push_back(n);
-  }
-  EvalJob ej1 = eval_launch(c, esrc, elen, xi, 0);
-  EvalJob ej2 = eval_launch(c, {Sc}, {n}, xiw, 1);
-  c.sync();
-  std::vector<Fr> ev1 = eval_finish(ej1);
-  const Fr sxiw = eval_finish(ej2)[0];
-  std::vector<Fr> fx(k), tx(k);
-  size_t p = 0;
-  for (int i = 0; i < k; i++) {
-    fx[i] = ev1[p++];
-    if (gs) tx[i] = ev1[p++];
-  }
-  Fr sFx = Fr::zero(), sTx = Fr::zero();
-  if (sel) {
-    sFx = ev1[p++];
-    sTx = ev1[p++];
-  }
-  const bool fxi_set = Fmut && vec;
-  const Fr fxi_mut = fxi_set ? ev1[p++] : Fr::zero();
-  std::vector<Fr> evals;  // proof order
-  for (int i = 0; i < k; i++) {
-    evals.push_back(fx[i]);
-    if (gs) evals.push_back(tx[i]);
-  }
-  if (sel) {
-    evals.push_back(sFx);
-    evals.push_back(sTx);
-  }
-  evals.push_back(sxiw);
-  lap(3);
-
-  // ---------------- round 5: linearisation + openings (prover.js:320-413)
-  tr.add_scalar(xi);
-  for (int i = 0; i < k; i++) {
-    tr.add_scalar(fx[i]);
-    if (gs) tr.add_scalar(tx[i]);
-  }
-  if (sel) {
-    tr.add_scalar(sFx);
-    tr.add_scalar(sTx);
-  }
-  tr.add_scalar(sxiw);
-  const Fr v = tr.challenge();
-  const R5 r5 = round5_terms(gs, sel, k, nbits, alpha, beta, gamma, v, xi, fx, tx, sFx, sTx, sxiw, lk,
-                             fxi_set ? &fxi_mut : nullptr);
-  LcTerms lw;
-  for (const R5Term& t : r5.terms) {
-    switch (t.id) {
-      case R5_S: lw.add(Sc, n, t.coef); break;
-      case R5_Q: lw.add(Qc, qlen, t.coef); break;
-      case R5_F: lw.add(Fc[t.idx], n, t.coef); break;
-      case R5_T: lw.add(Tc[t.idx], n, t.coef); break;
-      case R5_SELF: lw.add(sFc, n, t.coef); break;
-      case R5_SELT: lw.add(sTc, n, t.coef); break;
-      case R5_POLT: lw.add(polT, n, t.coef); break;
-    }
-  }
-  lw.c0 = r5.c0;
-  const Fr one = Fr::one();
-  uint32_t* Pbuf;
-  uint64_t L;
-  L = qlen > n ? qlen : n;
-  Pbuf = c.buf("Pw", 32 * L);
-  uint32_t* Wx = c.buf("Wxi", 32 * L);
-  const uint32_t* xp1 = xpowers(c, xi);
-  const uint32_t* xp2 = xpowers(c, xiw);
-  // two lanes: W_x's linear combination and division on lane 0 while W_xw's run on lane 1 (and its
-  // commitment starts there right after); the commitments balance as W_x[0, h) on lane 0 and W_xw +
-  // W_x[h, L - 1) on lane 1, h = half of all their points
-  fork_lanes(c);
-  run_lincomb(c.st, Pbuf, L, lw);
-  const uint32_t dtiles = (uint32_t)((L + EVAL_TILE - 1) / EVAL_TILE);
-  launch_divide(c.st, Wx, flags + 2, Pbuf, L, xp1, c.buf("div_part", 32 * (dtiles + 1)),
-                c.buf("div_carry", 32 * (dtiles + 1)));
-  // W_{xi w} = (S - S(xi w)) / (X - xi w)
-  LcTerms l2;
-  l2.add(Sc, n, one);
-  l2.c0 = sxiw.neg();
-  uint32_t* P2 = c.buf("Pw2", E);
-  uint32_t* Wxw = c.buf("Wxiw", E);
-  run_lincomb(s2, P2, n, l2);
-  launch_divide(s2, Wxw, flags + 3, P2, n, xp2, c.buf("div_part2", 32 * (ntiles + 1)),
-                c.buf("div_carry2", 32 * (ntiles + 1)));
-  check_launch();
-  Commit cW2 = commit_launch(c, Wxw, n - 1, slot++, 1);
-  lane_join(c, c.st, s2);  // W_x[h, L - 1) on lane 1 needs W_x
-  Commit cW1 = commit_launch_split(c, Wx, L - 1, (L - 1 + n - 1) / 2, slot);
-  slot += 2;
-  HC(hipMemcpyAsync(h_flags, flags, 64, hipMemcpyDeviceToHost, c.st));
-  c.sync();
-  if (h_flags[2] || h_flags[3]) throw KgsError(KGS_E_DOES_NOT_DIVIDE, "Polynomial does not divide");
-  commits_finish(c, {cW1, cW2}, {com[ci].data(), com[ci + 1].data()});
-  ci += 2;
-  lap(4);
-
-  for (int i = 0; i < ncom; i++) memcpy(com_out + 64 * i, com[i].data(), 64);
-  for (size_t i = 0; i < evals.size(); i++) evals[i].to_bytes(ev_out + 32 * i);
-  c.reset_staging();
+  if (in.nbits < 1) throw KgsError(KGS_E_ARG, "nbits must be >= 1");
+  check_srs(c, in.nbits);
+  if (in.nbits > c.nbits_max) throw KgsError(KGS_E_SRS, "SRS loaded for a smaller maximum domain; reload with larger nbits_max");
+  if (in.npols < 1) throw KgsError(KGS_E_ARG, "The number of multisets must be greater than 0.");
+  if (in.npols > KGS_MAX_POLS) throw KgsError(KGS_E_ARG, "too many multisets");
+  RoundOpts o;
+  o.hooks = &in;
+  o.piped_round1 = split_commits(c);
+  o.ref_quirks = c.ref_quirks && in.kind != KGS_LOOKUP;
+  prove_rounds(c, in.nbits, {in.arg()}, o, com_out, ev_out);
 }
-
 
 // ------------------------------------------------------------------ host G2 (synthetic ptau): host_pairing.hpp
 using host::Fq2;
@@ -1167,31 +729,25 @@ extern "C" {
 
 
 int kgs_ctx_create(int device, kgs_ctx_t** out) {
-  try {
-    if (!out) throw KgsError(KGS_E_ARG, "out is NULL");
-    int ndev = 0;
-    HC(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw KgsError(KGS_E_ARG, "no such HIP device");
-    HC(hipSetDevice(device));
-    auto* c = new kgs_ctx();
-    c->device = device;
-    HC(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    // the second MSM lane and the copy stream are created on first use: contexts that never need
-    // them keep one stream (several in-flight contexts share the device's few hardware queues)
-    c->d_scal = c->buf("scalars", kgs_ctx::SCAL_BYTES);
-    // reference-identical behaviour on degenerate inputs by default (kgs.h); KGS_REFERENCE_QUIRKS=0
-    // selects the exact-math prover
-    c->ref_quirks = true;
-    if (const char* e = getenv("KGS_REFERENCE_QUIRKS")) c->ref_quirks = e[0] != '0';
-    c->ensure_pin(8 << 20);
-    *out = c;
-    return KGS_OK;
-  } catch (const KgsError& e) {
-    return kgs_fail(e);
-  } catch (const std::exception& e) {
-    kgs_errbuf() = e.what();
-    return KGS_E_HIP;
-  }
+  API_BEGIN
+  if (!out) throw KgsError(KGS_E_ARG, "out is NULL");
+  int ndev = 0;
+  HC(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) throw KgsError(KGS_E_ARG, "no such HIP device");
+  HC(hipSetDevice(device));
+  auto* c = new kgs_ctx();
+  c->device = device;
+  HC(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+  // the second MSM lane and the copy stream are created on first use: contexts that never need
+  // them keep one stream (several in-flight contexts share the device's few hardware queues)
+  c->d_scal = c->buf("scalars", kgs_ctx::SCAL_BYTES);
+  // reference-identical behaviour on degenerate inputs by default (kgs.h); KGS_REFERENCE_QUIRKS=0
+  // selects the exact-math prover
+  c->ref_quirks = true;
+  if (const char* e = getenv("KGS_REFERENCE_QUIRKS")) c->ref_quirks = e[0] != '0';
+  c->ensure_pin(8 << 20);
+  *out = c;
+  API_END
 }
 
 void kgs_ctx_destroy(kgs_ctx_t* ctx) {
@@ -1201,17 +757,6 @@ void kgs_ctx_destroy(kgs_ctx_t* ctx) {
 }
 
 #define CTX_LOCK(c) std::lock_guard<std::mutex> ctx_lock_(c->mu)
-#define API_BEGIN try {
-#define API_END                               \
-  }                                           \
-  catch (const KgsError& e) {                 \
-    return kgs_fail(e);                           \
-  }                                           \
-  catch (const std::exception& e) {           \
-    kgs_errbuf() = e.what();                         \
-    return KGS_E_HIP;                         \
-  }                                           \
-  return KGS_OK;
 
 int kgs_device_count(int* count) {
   API_BEGIN
@@ -1627,22 +1172,6 @@ void stream_copy(uint8_t* dst, const uint8_t* src, size_t len, size_t dma, const
 // proofs): the registrations are reference-counted process-wide, so the first call to finish does not
 // unpin memory another call is still DMA-ing. Overlapping buffers with different starts fail to
 // register and take the staging path.
-// Drains every stream of the context when the call it guards leaves by an exception. Rank-group
-// contexts are left alone: their main stream may wait in an exchange whose peers failed (the group's
-// abort releases it), and they never DMA caller memory in place.
-struct DrainOnError {
-  kgs_ctx* ctx;
-  int unwinding = std::uncaught_exceptions();
-  explicit DrainOnError(kgs_ctx* c) : ctx(c) {}
-  ~DrainOnError() {
-    if (std::uncaught_exceptions() <= unwinding || ctx->group) return;
-    hipSetDevice(ctx->device);
-    for (hipStream_t s : {ctx->st, ctx->st2, ctx->st_copy, ctx->st_wb})
-      if (s) (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-  }
-};
-
 static std::mutex g_pin_mu;
 static std::map<void*, std::pair<size_t, int>> g_pins;  // start -> (bytes, calls holding it)
 struct HostPins {
@@ -1901,7 +1430,7 @@ int kgs_prove(kgs_ctx_t* ctx, int kind, int nbits, int npols, const uint8_t* con
     if (wait_f0) HC(hipEventRecord(ctx->ev_in[0], ctx->st));
     for (size_t v = 1; v < in_jobs.size(); v++) in.ready[v] = ctx->ev_in[v];
     // vectors 1.. are copied into their pinned slots and DMA'd by a feeder thread while the prover
-    // already enqueues (and the GPU runs) vector 0's work; prove_impl waits for a vector's DMA to be
+    // already enqueues (and the GPU runs) vector 0's work; prove_rounds waits for a vector's DMA to be
     // ENQUEUED (input_issued) before its kernels wait on the vector's event
     if (in_jobs.size() > 1) {
       feeder.t = std::thread([&, dev = ctx->device] {

@@ -464,18 +464,9 @@ void dist_preconditions(kgs_ctx& c, const ProveIn& in) {
 }
 
 void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out) {
-  using clk = std::chrono::steady_clock;
-  auto t0 = clk::now();
   c.timing.resize(9, 0.0);
   for (int i = 0; i < 6; i++) c.timing[i] = 0.0;
-  Range range(ROUND_NAMES[0]);
-  auto lap = [&](int rr) {
-    auto t1 = clk::now();
-    c.timing[rr] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    t0 = t1;
-    if (rr + 1 < 5) range.push(ROUND_NAMES[rr + 1]);
-    else range.pop();
-  };
+  RoundClock clock(c);
   Dist D(c);
   const int W = D.W, r = D.r, logW = D.logW;
   const bool gs = in.kind != KGS_GRANDPRODUCT;  // KGS_LOOKUP is a selected grand-sum
@@ -559,7 +550,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
     for (size_t i = 0; i < r1.size(); i++) outs.push_back(com[ci++].data());
     commits_finish_with(c, r1, outs, W, D.host_ag());
   }
-  lap(0);
+  clock.lap(0);
 
   // ---------------- round 2: challenges, combined polynomials, S / Z (prover.js:181-231)
   host::Transcript tr;
@@ -660,7 +651,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   c.sync();
   const int iS = ci;
   commits_finish_with(c, {cS}, {com[ci++].data()}, W, D.host_ag());
-  lap(1);
+  clock.lap(1);
 
   // ---------------- round 3: quotient on a coset (prover.js:233-286)
   tr.add_scalar(gamma);
@@ -765,7 +756,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   }
   const int iQ = ci;
   commits_finish_with(c, {cQ}, {com[ci++].data()}, W, D.host_ag());
-  lap(2);
+  clock.lap(2);
 
   // ---------------- round 4: evaluations (prover.js:288-318): Horner on CYCLIC slices at x^W
   tr.add_scalar(alpha);
@@ -773,23 +764,18 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   const Fr xi = tr.challenge();
   const Fr w = fr_w(nbits);
   const Fr xiw = xi * w;
+  const ArgIn arg = in.arg();
+  ArgPolys P;  // this rank's slices
+  P.Fc = Fc;
+  P.Tc = Tc;
+  P.sFc = sFc;
+  P.sTc = sTc;
+  P.Sc = Sc;
+  P.polT = polT;
+  P.Qc = Qc;
   std::vector<const uint32_t*> esrc;
-  std::vector<uint64_t> elen;
-  for (int i = 0; i < k; i++) {
-    esrc.push_back(Fc[i]);
-    elen.push_back(M);
-    if (gs) {
-      esrc.push_back(Tc[i]);
-      elen.push_back(M);
-    }
-  }
-  if (sel) {
-    esrc.push_back(sFc);
-    elen.push_back(M);
-    esrc.push_back(sTc);
-    elen.push_back(M);
-  }
-  EvalJob ej1 = eval_launch(c, esrc, elen, xi.pow_u64((uint64_t)W), 0);
+  arg.each_xi(false, [&](R5Poly id, int i) { esrc.push_back(P.poly(id, i)); });
+  EvalJob ej1 = eval_launch(c, esrc, std::vector<uint64_t>(esrc.size(), M), xi.pow_u64((uint64_t)W), 0);
   EvalJob ej2 = eval_launch(c, {Sc}, {M}, xiw.pow_u64((uint64_t)W), 1);
   c.sync();
   std::vector<Fr> loc = eval_finish(ej1);
@@ -807,55 +793,20 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
       xwr = xwr * xiw;
     }
   }
-  std::vector<Fr> fx(k), tx(k);
-  size_t p = 0;
-  for (int i = 0; i < k; i++) {
-    fx[i] = ev1[p++];
-    if (gs) tx[i] = ev1[p++];
-  }
-  Fr sFx = Fr::zero(), sTx = Fr::zero();
-  if (sel) {
-    sFx = ev1[p++];
-    sTx = ev1[p++];
-  }
-  std::vector<Fr> evals;  // proof order
-  for (int i = 0; i < k; i++) {
-    evals.push_back(fx[i]);
-    if (gs) evals.push_back(tx[i]);
-  }
-  if (sel) {
-    evals.push_back(sFx);
-    evals.push_back(sTx);
-  }
+  XiEvals x;
+  x.unpack(arg, ev1.data());
+  std::vector<Fr> evals = ev1;  // proof order
   evals.push_back(sxiw);
-  lap(3);
+  clock.lap(3);
 
   // ---------------- round 5: linearisation + openings (prover.js:320-413)
   tr.add_scalar(xi);
-  for (int i = 0; i < k; i++) {
-    tr.add_scalar(fx[i]);
-    if (gs) tr.add_scalar(tx[i]);
-  }
-  if (sel) {
-    tr.add_scalar(sFx);
-    tr.add_scalar(sTx);
-  }
-  tr.add_scalar(sxiw);
+  for (const Fr& e : evals) tr.add_scalar(e);
   const Fr v = tr.challenge();
-  const R5 r5 = round5_terms(gs, sel, k, nbits, alpha, beta, gamma, v, xi, fx, tx, sFx, sTx, sxiw, lk);
+  const R5 r5 = round5_terms(gs, sel, k, nbits, alpha, beta, gamma, v, xi, x.fx, x.tx, x.sFx, x.sTx, sxiw, lk);
   const uint64_t qcnt = qlen > (uint64_t)r ? (qlen - r + W - 1) / W : 0;
   LcTerms lw;
-  for (const R5Term& t : r5.terms) {
-    switch (t.id) {
-      case R5_S: lw.add(Sc, M, t.coef); break;
-      case R5_Q: lw.add(Qc, qcnt, t.coef); break;
-      case R5_F: lw.add(Fc[t.idx], M, t.coef); break;
-      case R5_T: lw.add(Tc[t.idx], M, t.coef); break;
-      case R5_SELF: lw.add(sFc, M, t.coef); break;
-      case R5_SELT: lw.add(sTc, M, t.coef); break;
-      case R5_POLT: lw.add(polT, M, t.coef); break;
-    }
-  }
+  for (const R5Term& t : r5.terms) lw.add(P.poly(t.id, t.idx), t.id == R5_Q ? qcnt : M, t.coef);
   lw.c0 = r == 0 ? r5.c0 : Fr::zero();  // the constant term lives at global index 0 (rank 0)
   const uint64_t L = qlen > n ? qlen : n;
   // numerator P (CYCLIC over cs >= L points) -> BLOCK -> division by (X - xi) with carries
@@ -918,7 +869,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   c.sync();
   commits_finish_with(c, {cW1, cW2}, {com[ci].data(), com[ci + 1].data()}, W, D.host_ag());
   ci += 2;
-  lap(4);
+  clock.lap(4);
 
   for (int i = 0; i < ncom_all; i++) memcpy(com_out + 64 * i, com[i].data(), 64);
   for (size_t i = 0; i < evals.size(); i++) evals[i].to_bytes(ev_out + 32 * i);
@@ -957,17 +908,6 @@ void prove_dist_group(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* 
 }  // namespace kgsi
 
 // ================================================================== C-ABI
-#define API_BEGIN try {
-#define API_END                               \
-  }                                           \
-  catch (const KgsError& e) {                 \
-    return kgs_fail(e);                       \
-  }                                           \
-  catch (const std::exception& e) {           \
-    kgs_errbuf() = e.what();                  \
-    return KGS_E_HIP;                         \
-  }                                           \
-  return KGS_OK;
 
 static void check_world(int world) {
   if (world < 1 || world > 16 || (world & (world - 1))) throw KgsError(KGS_E_ARG, "group world must be 1, 2, 4, 8 or 16");

@@ -263,23 +263,13 @@ int verify_batch_impl(kgs_ctx* ctx, const kgs_proof_ref_t* proofs, int count, co
 
 }  // namespace
 
-#define VB_API_END                   \
-  catch (const KgsError& e) {        \
-    return kgs_fail(e);              \
-  }                                  \
-  catch (const std::exception& e) {  \
-    kgs_errbuf() = e.what();         \
-    return KGS_E_HIP;                \
-  }
-
 extern "C" {
 
 int kgs_verify_batch(kgs_ctx_t* ctx, const kgs_proof_ref_t* proofs, int count, const uint8_t tau_g2[128],
                      uint8_t* valid_out, kgs_batch_diag_t* diag) {
-  try {
-    return verify_batch_impl(ctx, proofs, count, tau_g2, valid_out, diag);
-  }
-  VB_API_END
+  API_BEGIN
+  return verify_batch_impl(ctx, proofs, count, tau_g2, valid_out, diag);
+  API_END
 }
 
 int kgs_verify_batch_ptau(kgs_ctx_t* ctx, const char* ptau_path, const kgs_proof_ref_t* proofs, int count,
@@ -292,23 +282,21 @@ int kgs_verify_batch_ptau(kgs_ctx_t* ctx, const char* ptau_path, const kgs_proof
 
 int kgs_g1_lincomb(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, const uint64_t* seg_off,
                    uint64_t nseg, uint8_t* out_lem) {
-  try {
-    if (!seg_off || (nseg && !out_lem)) throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: NULL argument");
-    check_segments(seg_off, nseg);
-    const uint64_t nterms = seg_off[nseg];
-    if (nterms && (!points_lem || !scalars_std)) throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: NULL argument");
-    for (uint64_t t = 0; t < nterms; t++)
-      if (!host::g1_valid(points_lem + 64 * t))
-        throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: point " + std::to_string(t) + " is not on the curve");
-    CtxUse use(ctx, "kgs_g1_lincomb");
-    if (!nseg) return KGS_OK;
-    if (ctx)
-      fold_gpu(*ctx, points_lem, scalars_std, seg_off, nseg, out_lem);
-    else
-      fold_host(points_lem, scalars_std, seg_off, nseg, out_lem);
-    return KGS_OK;
-  }
-  VB_API_END
+  API_BEGIN
+  if (!seg_off || (nseg && !out_lem)) throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: NULL argument");
+  check_segments(seg_off, nseg);
+  const uint64_t nterms = seg_off[nseg];
+  if (nterms && (!points_lem || !scalars_std)) throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: NULL argument");
+  for (uint64_t t = 0; t < nterms; t++)
+    if (!host::g1_valid(points_lem + 64 * t))
+      throw KgsError(KGS_E_ARG, "kgs_g1_lincomb: point " + std::to_string(t) + " is not on the curve");
+  CtxUse use(ctx, "kgs_g1_lincomb");
+  if (!nseg) return KGS_OK;
+  if (ctx)
+    fold_gpu(*ctx, points_lem, scalars_std, seg_off, nseg, out_lem);
+  else
+    fold_host(points_lem, scalars_std, seg_off, nseg, out_lem);
+  API_END
 }
 
 }  // extern "C"

@@ -215,6 +215,63 @@ def test_failures_name_the_argument_and_leave_the_context_usable(K, ctx, nbits):
             MO.prove_multi(MC.srs(), bad)
 
 
+# ------------------------------------------------------------------ 5b. one round engine, two entry points
+# (csrc/prover_rounds.cpp: the single and the multi prover share the rounds, the work buffers and the flag words)
+def _single(ctx, a, nbits):
+    coms, evs = ctx.prove(MC.KIND[a["kind"]], nbits, a["Fs"], a["Ts"], a["selF"], a["selT"], mont_out=False)[:2]
+    return tuple(coms), tuple(evs)
+
+
+def _builder_fails(nbits):
+    """argument 1 of the mix of test_failures_name_the_argument_and_leave_the_context_usable with that test's
+    one changed value in its T: a grand-product (k = 2) whose Z is not well calculated"""
+    a = MC.arguments("gs3sel,gp2,lookup,gpsel", nbits)[1]
+    t = bytearray(a["Ts"][1])
+    t[64:96] = ((int.from_bytes(t[64:96], "little") + 1) % R).to_bytes(32, "little")
+    return dict(a, Ts=[a["Ts"][0], bytes(t)])
+
+
+@pytest.mark.parametrize("case", [("gs3sel,gp2,lookup,gpsel", 5), ("alt9", 3), ("gp,gp", 1)], ids=MC.case_id)
+def test_one_lane_equals_two_lanes(ctx, case):
+    mix, nbits = case
+    args = MC.arguments(mix, nbits)
+    try:
+        ctx.set_msm_lanes(1)
+        one = prove(ctx, args, nbits)
+        ctx.set_msm_lanes(2)
+        two = prove(ctx, args, nbits)
+    finally:
+        ctx.set_msm_lanes(2)
+    assert one == MC.restated(mix, nbits)
+    assert two == MC.restated(mix, nbits)
+
+
+def test_both_entry_points_interleaved_on_one_context(K, ctx):
+    mix, mbits = "gs3sel,gp2,lookup,gpsel", 5
+    margs = MC.arguments(mix, mbits)
+    Fs, Ts, sF, sT = common.make_inputs(77, 8, 1, True)
+    sarg = {"kind": "grandproduct", "Fs": Fs, "Ts": Ts, "selF": sF, "selT": sT}
+    single1 = _single(ctx, sarg, 8)
+    multi1 = prove(ctx, margs, mbits)
+    assert multi1 == MC.restated(mix, mbits)
+    with pytest.raises(K.KgsError, match="^The grand-product polynomial Z is not well calculated$") as e:
+        _single(ctx, _builder_fails(mbits), mbits)
+    assert e.value.code == E_NOT_WELL_CALC
+    assert prove(ctx, margs, mbits) == multi1
+    assert _single(ctx, sarg, 8) == single1
+
+
+def test_only_the_multi_entry_point_names_the_argument(K, ctx):
+    nbits = 5
+    bad = _builder_fails(nbits)
+    with pytest.raises(K.KgsError, match="^argument 0: The grand-product polynomial Z is not well calculated$") as em:
+        prove(ctx, [bad], nbits)
+    with pytest.raises(K.KgsError, match="^The grand-product polynomial Z is not well calculated$") as es:
+        _single(ctx, bad, nbits)
+    assert em.value.code == es.value.code == E_NOT_WELL_CALC
+    assert ctx.idle() is True
+
+
 def test_argument_errors(K, ctx):
     nbits = 3
     good = MC.native_args(MC.arguments("gs,gp,lookup", nbits))
