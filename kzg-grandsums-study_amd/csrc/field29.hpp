@@ -364,8 +364,10 @@ struct g1_acc29 {
   // combine and bit-sum trees. 10 products + 2 squares + the lazily reduced Y3. The CIOS rows give
   // 9 independent column chains, so a lone wave (these trees run at low occupancy) is far less
   // latency-bound than with the 8 x 32-bit product-scanning chain. Special cases as g1_xyzz::add;
-  // the doubling (equal points, never met by distinct buckets in practice) goes through the 256-bit
-  // path and is converted back.
+  // the doubling (equal points: never met by the buckets of an SRS of distinct points, met at every
+  // level of the trees when the SRS repeats a point) goes through the 256-bit path and is converted
+  // back. The equal, opposite and infinity cases of add and add_aff run on the device in
+  // tests/test_gpu_degenerate_srs.py, on SRS files whose points coincide, cancel or are zero.
   __device__ __forceinline__ void add(const g1_acc29& o) {
     if (o.inf) return;
     if (inf) {

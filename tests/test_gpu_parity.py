@@ -89,6 +89,40 @@ def test_ntt(ctx9, logm):
     assert unmb(ctx9.ntt(common.mont_bytes(v), True)) == OP.ntt(v, True)
 
 
+# the largest value below r whose seven low 32-bit limbs are all 0xffffffff
+_LOW_ONES = (((R >> 224) - 1) << 224) | ((1 << 224) - 1)
+
+
+def _ntt_extreme_input(kind, m):
+    """-> Montgomery bytes of an m-element vector at the edge of the field"""
+    if kind == "all":
+        return common.mont_bytes([R - 1] * m)
+    if kind == "alternating":
+        return common.mont_bytes([R - 1 if i % 2 == 0 else 0 for i in range(m)])
+    if kind == "first":
+        return common.mont_bytes([R - 1] + [0] * (m - 1))
+    if kind == "last":
+        return common.mont_bytes([0] * (m - 1) + [R - 1])
+    # raw Montgomery words (the bytes themselves, not the Montgomery form of these values)
+    words = {"raw_r-1": [R - 1], "raw_r-2": [R - 2], "raw_low_ones": [_LOW_ONES],
+             "raw_cycle": [R - 1, R - 2, _LOW_ONES]}[kind]
+    return b"".join(words[i % len(words)].to_bytes(32, "little") for i in range(m))
+
+
+# one size per pass plan listed above test_ntt. The lazy butterflies keep values in [0, 2r) and
+# [0, 4r): inputs at the top of the canonical range (values r - 1, and the raw words r - 1, r - 2
+# and 0x...ffffffff) are where a missing conditional subtraction shows
+@pytest.mark.parametrize("kind", ["all", "alternating", "first", "last", "raw_r-1", "raw_r-2", "raw_low_ones",
+                                  "raw_cycle"])
+@pytest.mark.parametrize("logm", [0, 1, 2, 3, 5, 10, 11, 13, 14, 17])
+def test_ntt_extremes(ctx9, logm, kind):
+    assert _LOW_ONES < R
+    x = _ntt_extreme_input(kind, 1 << logm)
+    v = unmb(x)
+    assert unmb(ctx9.ntt(x, False)) == OP.ntt(v, False)
+    assert unmb(ctx9.ntt(x, True)) == OP.ntt(v, True)
+
+
 # 18..22: three-pass plans with up to 9 stages in one pass (lds_plan: 9+9, 6+6+7, 6+6+8, 6+6+9, 7+6+9),
 # byte-for-byte against the C restatement's transform (oracle.c ntt)
 @pytest.mark.parametrize("logm", [18, 19, 20, 21, 22])
@@ -329,6 +363,25 @@ def test_eval_and_division(ctx9, L):
     c[0] = (c[0] + 1) % R
     K = common.load_pkg()
     with pytest.raises(K.KgsError, match="Polynomial does not divide"):
+        ctx9.poly_div_x_sub(common.mont_bytes(c), bn.fr_to_bytes(x))
+
+
+@pytest.mark.parametrize("x", [0, 1, R - 1, None], ids=["x0", "x1", "xr-1", "xrandom"])
+@pytest.mark.parametrize("coef", ["max", "random"])
+@pytest.mark.parametrize("L", [2, 2049])
+def test_eval_and_division_extremes(ctx9, L, coef, x):
+    """test_eval_and_division at the edges of the field: every coefficient r - 1, and the evaluation
+    points 0, 1 and r - 1 (L = 2049 crosses the 2048-coefficient chunks of the Horner kernels)."""
+    rnd = random.Random(L)
+    c = [R - 1] * L if coef == "max" else rv(rnd, L)
+    if x is None:
+        x = rnd.randrange(R)
+    assert bn.fr_from_bytes(ctx9.poly_eval(common.mont_bytes(c), bn.fr_to_bytes(x))) == OP.Polynomial(c).evaluate(x)
+    c[0] = (c[0] - OP.Polynomial(c).evaluate(x)) % R
+    q = unmb(ctx9.poly_div_x_sub(common.mont_bytes(c), bn.fr_to_bytes(x)))
+    assert q == OP.Polynomial(list(c)).div_by_x_sub_value(x).coef
+    c[0] = (c[0] + R - 1) % R
+    with pytest.raises(common.load_pkg().KgsError, match="Polynomial does not divide"):
         ctx9.poly_div_x_sub(common.mont_bytes(c), bn.fr_to_bytes(x))
 
 
