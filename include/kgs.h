@@ -442,6 +442,31 @@ int kgs_lookup_multiplicities_device(kgs_ctx_t* ctx, int npols, uint64_t n, cons
  * kgs_lookup_multiplicities (mutex, no rank group, idle on return). */
 int kgs_g1_lincomb(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, const uint64_t* seg_off,
                    uint64_t nseg, uint8_t* out_lem);
+/* Variable-base MSM ([ffjs] G1.multiExpAffine over arbitrary bases): out_lem = sum_i s_i * P_i for
+ * i < n. No window tables are built: the points are read as given (one 64 B row, O(n) device memory),
+ * where kgs_msm runs over the resident SRS tables that kgs_srs_load_* expands once.
+ *   points_lem   n affine LEM points, 64 B each; 64 zero bytes is the identity, allowed anywhere.
+ *                Points are NOT validated (as for kgs_srs_load_points and [ffjs]): a point off the
+ *                curve or a coordinate >= q gives an unspecified result, never a fault.
+ *   scalars_std  n x 32 B little-endian STANDARD form; any 256-bit integer, taken mod r (which is the
+ *                integer multiple for every point of G1: the cofactor is 1)
+ *   n            0 .. 2^26; n == 0 gives the identity
+ *   window_c     0: the library chooses (clamp(ceil(log2 n) - 4, 7, 16)); 7 .. 16: that window, used as
+ *                given (for tests and tuning; with window_c == 7, n <= 2^31 / 37)
+ *   out_lem      affine LEM, the identity as 64 zero bytes
+ * ctx == NULL computes on the host (no GPU is touched; window_c is only range-checked).
+ * Failures: KGS_E_ARG for a window_c outside {0, 7 .. 16}, a NULL buffer with n > 0, n above the limit,
+ * a context attached to a rank group (kgs_ctx_set_group) or with MSM sharding on (kgs_ctx_set_shard).
+ * Same context contract as kgs_lookup_multiplicities and kgs_g1_lincomb: the call holds the context's
+ * mutex, uses device buffers of its own (sized from n and the window), needs no SRS and leaves the
+ * resident SRS, the domain tables and the prover's MSM work buffers as they are, and returns with nothing
+ * pending on the context's streams, on its error paths too (kgs_ctx_idle). */
+int kgs_msm_points(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t n, int window_c,
+                   uint8_t out_lem[64]);
+/* Same with device pointers (on ctx's device; ctx must not be NULL). Both buffers are read only: the
+ * points are copied into a buffer of the library's own before they are converted. */
+int kgs_msm_points_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t n,
+                          int window_c, uint8_t out_lem[64]);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 

@@ -150,6 +150,9 @@ def lib():
                                             c_u8p]
         L.kgs_g1_lincomb.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
                                      c_u8p]
+        L.kgs_msm_points.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p]
+        L.kgs_msm_points_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.c_int, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.kgs_ctx_set_reference_quirks.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -607,6 +610,18 @@ class Context:
     def g1_lincomb(self, points_lem, scalars_std, seg_off):
         """Segmented G1 linear combination on the GPU (kgs_g1_lincomb): see the module-level g1_lincomb."""
         return _g1_lincomb(self._h, points_lem, scalars_std, seg_off)
+
+    def msm_points(self, points_lem, scalars_std, window_c=0):
+        """Variable-base MSM on the GPU (kgs_msm_points): see the module-level msm_points."""
+        return _msm_points(self._h, points_lem, scalars_std, window_c)
+
+    def msm_points_device(self, d_points, d_scalars, n, window_c=0):
+        """Device-resident twin (kgs_msm_points_device): d_points / d_scalars are device pointers (ints)
+        to n affine LEM points of 64 B and n standard-form scalars of 32 B, both read only. Returns the
+        64 B affine LEM sum."""
+        out = ctypes.create_string_buffer(64)
+        _check(lib().kgs_msm_points_device(self._h, d_points, d_scalars, n, window_c, out))
+        return out.raw
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1134,6 +1149,27 @@ def g1_lincomb(points_lem, scalars_std, seg_off, device=0):
     identity). device=None computes on the host."""
     handle = None if device is None else _context(device).handle
     return _g1_lincomb(handle, points_lem, scalars_std, seg_off)
+
+
+def _msm_points(handle, points_lem, scalars_std, window_c):
+    if len(points_lem) % 64 or len(scalars_std) % 32 or len(points_lem) // 64 != len(scalars_std) // 32:
+        raise ValueError("points_lem / scalars_std must hold the same number of 64 B points / 32 B scalars")
+    n = len(points_lem) // 64
+    out = ctypes.create_string_buffer(64)
+    (pp, kp), (ps, ks) = _ptr(points_lem), _ptr(scalars_std)  # read in place
+    _check(lib().kgs_msm_points(handle, pp if n else None, ps if n else None, n, window_c, out))
+    del kp, ks
+    return out.raw
+
+
+def msm_points(points_lem, scalars_std, device=0, window_c=0):
+    """sum_i scalars[i] * points[i] over arbitrary bases (kgs_msm_points), without window tables: points
+    64 B affine LEM (the zero point allowed, points are not validated), scalars 32 B little-endian
+    standard form (any 256-bit integer, taken mod r). Returns 64 B affine LEM (zeros for the identity).
+    window_c: 0 lets the library choose, 7 .. 16 sets the Pippenger window. device=None computes on the
+    host."""
+    handle = None if device is None else _context(device).handle
+    return _msm_points(handle, points_lem, scalars_std, window_c)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

@@ -188,6 +188,22 @@ void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int 
 // tails); default: a 168-VGPR build that leaves room for other proofs' kernels (msm.hip).
 void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N, uint32_t* T_out,
              hipEvent_t* ev = nullptr, uint64_t pbase = 0, uint64_t pstride = 1, bool exclusive_acc = false);
+// Variable-base MSM over one row of points, no window tables (msm.hip). Window c in
+// MSM_POINTS_C_MIN .. MSM_POINTS_C_MAX: W = ceil(255 / c) windows of B = 2^(c-1) buckets each, and
+// W * B <= 2^19 is the largest key space the sort partitions (c = 16 reaches it exactly). The partition
+// pass stages 256 * 2 * W * 7 B + 12 B per partition in LDS: 133.0 KB at c = 7, of a workgroup's 160 KB.
+constexpr int MSM_POINTS_C_MIN = 7, MSM_POINTS_C_MAX = 16;
+struct MsmPointsSizes {  // bytes of the MsmWork buffers (same roles as in msm_run) and of the T output
+  uint64_t digit, sorted, lo, blockhist, counts, offsets, cursor, segowner, locnt, chunklist, raw29, part, T;
+};
+MsmPointsSizes msm_points_sizes(uint64_t N, int c);
+// row (N affine points, 256-bit Montgomery, zeros = identity) -> the accumulation's 29-bit form, in place
+void msm_points_row29(hipStream_t st, uint32_t* row, uint64_t N);
+// T_out[j * c + k] (XYZZ, 128 B) = sum of window j's buckets with bit k set, so that
+// sum_i s_i P_i = sum_m 2^m T_out[m] over m < W * c. scalars_std: N x 8 words, any 256-bit integers (taken
+// mod r). N >= 1, N * W <= 2^31; w sized by msm_points_sizes(N, c).
+void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
+                    uint32_t* T_out);
 void launch_fixed_base(hipStream_t st, uint32_t* out_xyzz, const uint32_t* sc, uint64_t count, const uint32_t* tbl);
 void launch_batch_affine(hipStream_t st, uint32_t* out_aff, const uint32_t* in_xyzz, uint32_t* scratch, uint64_t npts);
 

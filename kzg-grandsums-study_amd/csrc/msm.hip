@@ -103,12 +103,18 @@ void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int 
 //          through LDS (again run-wise stores), and writes the bucket offsets.
 // Order inside a bucket is unspecified (point addition is commutative).
 // digits of scalar i: from the Montgomery-form scalars (STD = false) or from their standard forms
-// (STD = true: k_sort_hist stores them for k_sort_part, which then skips the conversion)
-template <int C, bool STD = false>
+// (STD = true: k_sort_hist stores them for k_sort_part, which then skips the conversion). RED (the
+// variable-base MSM's histogram pass): the standard form is any 256-bit integer and is reduced mod r
+// first, by at most 5 conditional subtractions (2^256 / r < 6).
+template <int C, bool STD = false, bool RED = false>
 __device__ __forceinline__ void scalar_digits(int32_t (&d)[(255 + C - 1) / C], const uint32_t* sc, uint64_t i,
                                               uint32_t* std_out = nullptr) {
   constexpr int W = (255 + C - 1) / C;
   fr s = STD ? fr::load(sc + 8 * i) : fr::load(sc + 8 * i).from_mont();
+  if (RED) {
+#pragma unroll
+    for (int k = 0; k < 5; k++) s = fr::reduce_once(s);
+  }
   if (std_out) s.store(std_out + 8 * i);
   constexpr int32_t half = 1 << (C - 1);
   constexpr uint32_t mask = (1u << C) - 1;
@@ -182,12 +188,22 @@ __device__ __forceinline__ uint32_t block_excl_scan(const uint32_t* a, uint32_t*
 // partition of a nonzero digit magnitude: (key - 1) >> lob
 __device__ __forceinline__ uint32_t part_of(uint32_t key, int lob) { return (key - 1) >> lob; }
 
+// Sort key of window j's digit magnitude m in [1, B], B = 2^(C-1). Fixed base (VAR = false): m, one
+// bucket set shared by all windows (the window is in the table row). Variable base (VAR = true, the
+// table-less MSM over one row of points, msm_points_run): j * B + m in [1, W * B], a bucket set per
+// window.
+template <int C, bool VAR>
+__device__ __forceinline__ uint32_t sort_key(int j, uint32_t m) {
+  return VAR ? (uint32_t)j * (1u << (C - 1)) + m : m;
+}
+
 #ifndef KGS_SORT_SPT
 #define KGS_SORT_SPT 2
 #endif
 constexpr int SORT_SPT = KGS_SORT_SPT;  // scalars per thread in the histogram / partition passes
 
-template <int C>
+// VAR: the scalars are standard forms of any 256-bit integer (reduced here), keys by sort_key
+template <int C, bool VAR = false>
 __global__ void __launch_bounds__(256) k_sort_hist(uint32_t* __restrict__ bh, const uint32_t* __restrict__ sc,
                                                    uint64_t N, int lob, int NH, uint32_t nblk,
                                                    uint32_t* __restrict__ std_out) {
@@ -201,10 +217,11 @@ __global__ void __launch_bounds__(256) k_sort_hist(uint32_t* __restrict__ bh, co
     const uint64_t i = ((uint64_t)blockIdx.x * SORT_SPT + q) * 256 + threadIdx.x;
     if (i < N) {
       int32_t d[W];
-      scalar_digits<C>(d, sc, i, std_out);
+      if (VAR) scalar_digits<C, true, true>(d, sc, i, std_out);
+      else scalar_digits<C>(d, sc, i, std_out);
 #pragma unroll
       for (int j = 0; j < W; j++) {
-        if (d[j]) atomicAdd(&h[part_of((uint32_t)(d[j] < 0 ? -d[j] : d[j]), lob)], 1u);
+        if (d[j]) atomicAdd(&h[part_of(sort_key<C, VAR>(j, (uint32_t)(d[j] < 0 ? -d[j] : d[j])), lob)], 1u);
       }
     }
   }
@@ -267,8 +284,9 @@ __global__ void __launch_bounds__(256) k_sort_scan(uint32_t* __restrict__ hi_off
 
 // dynamic LDS (part_lds in msm_run): NS = 256 * SORT_SPT * W staged entries (4 B value, 2 B partition,
 // 1 B lo) and the block's per-partition base / offset / cursor (3 x NH words)
-// scalar i multiplies SRS point pbase + pstride * i (a contiguous or strided slice of the SRS)
-template <int C>
+// scalar i multiplies SRS point pbase + pstride * i (a contiguous or strided slice of the SRS).
+// VAR: keys by sort_key, and the entry's value is the point index i into the single row.
+template <int C, bool VAR = false>
 __global__ void __launch_bounds__(256) k_sort_part(uint32_t* __restrict__ tval, uint8_t* __restrict__ tlo,
                                                    const uint32_t* __restrict__ bh, const uint32_t* __restrict__ ptot,
                                                    const uint32_t* __restrict__ hi_off, const uint32_t* __restrict__ sc,
@@ -306,10 +324,10 @@ __global__ void __launch_bounds__(256) k_sort_part(uint32_t* __restrict__ tval, 
 #pragma unroll
       for (int j = 0; j < W; j++) {
         if (!d[j]) continue;
-        const uint32_t k = (uint32_t)(d[j] < 0 ? -d[j] : d[j]);
+        const uint32_t k = sort_key<C, VAR>(j, (uint32_t)(d[j] < 0 ? -d[j] : d[j]));
         const uint32_t p = part_of(k, lob);
         const uint32_t pos = atomicAdd(&cur[p], 1u);
-        sval[pos] = ((uint32_t)j * (uint32_t)Nsrs + pidx) | (d[j] < 0 ? 0x80000000u : 0u);
+        sval[pos] = (VAR ? (uint32_t)i : (uint32_t)j * (uint32_t)Nsrs + pidx) | (d[j] < 0 ? 0x80000000u : 0u);
         spart[pos] = (uint16_t)p;
         slo[pos] = (uint8_t)((k - 1) - (p << lob));
       }
@@ -991,6 +1009,72 @@ __global__ void __launch_bounds__(128) k_bitsum_rc(uint32_t* __restrict__ T, con
 }
 
 // ------------------------------------------------------------------ driver (device part)
+// The part of an MSM behind its partition pass, shared by the fixed-base driver (msm_run) and the
+// variable-base one (msm_points_run): the lo pass over NH partitions of 2^lob keys, the bucket
+// accumulation of the E (upper bound) sorted entries against the points at `table`, and the bucket
+// totals, which replace records 1 .. B of w.raw29. ev: msm_run's events [1] .. [2].
+static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, uint64_t E, int NH, int lob, uint32_t B,
+                        bool exclusive_acc, hipEvent_t* ev) {
+  uint32_t* hi_off = w.cursor;
+  uint32_t* cpre = w.cursor + NH_MAX + 8;
+  uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
+  // lo-pass grid: an upper bound of sum_p chunk_count(size_p) (blocks past cpre[NH] exit)
+  const uint64_t chunk_bound = std::min<uint64_t>((uint64_t)NH * SL_G, NH + E / SL_CHUNK);
+  hipLaunchKernelGGL(k_lo_count, dim3((unsigned)chunk_bound), dim3(LC_THREADS), 0, st, w.locnt, w.lo, hi_off, cpre,
+                     bpart, NH, lob);
+  hipLaunchKernelGGL(k_lo_scatter, dim3((unsigned)chunk_bound), dim3(SL_THREADS), 0, st, w.sorted, w.offsets, w.locnt,
+                     (const uint32_t*)w.digit, w.lo, hi_off, cpre, bpart, NH, lob);
+  if (ev) hipEventRecord(ev[1], st);
+  // one segment per resident thread (KGS_ACC_WAVES blocks of 256 per CU): every accumulate
+  // thread runs once and they all finish together (a second, partial round of blocks would
+  // leave most of the chip idle for a whole segment's duration)
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    return n;
+  }();
+  const uint64_t resident = (uint64_t)cus * KGS_ACC_WAVES * 256;
+  uint64_t L = (E + resident - 1) / resident;
+  if (L < 4) L = 4;
+  if ((E + L - 1) / L > (1ull << 18)) L = (E + (1ull << 18) - 1) >> 18;  // work buffers hold 2^18 + 2^16 segments
+  const uint64_t nseg = (E + L - 1) / L;
+  // chunk lists of the combine levels: list j holds <= nseg / CB_T^(j+1) + B entries
+  uint32_t* cnt = w.chunkcnt;
+  const uint64_t lcap = nseg / CB_T + B + 16;
+  hipMemsetAsync(cnt, 0, 4 * CB_LEVELS, st);
+  // progress priority (k_accumulate): KGS_ACC_PRIO 0 off, 1 the exclusive (two-lane) build, 2 every launch
+  static const int acc_prio = [] {
+    const char* e = getenv("KGS_ACC_PRIO");
+    return e ? atoi(e) : 1;
+  }();
+  // steps at 3/4 and 93/100 of the segment (a two-wave issue model with the leftover rate of the
+  // younger wave measured alone, 0.34 of the older's, puts these within 1 % of the best pair)
+#ifdef KGS_NO_PRIO_AUX
+  const bool prio = false;  // the A/B build without wave priorities: no step priority either
+  (void)acc_prio;
+#else
+  const bool prio = acc_prio >= 2 || (acc_prio == 1 && exclusive_acc);
+#endif
+  const uint32_t pm1 = prio ? (uint32_t)(3 * L / 4) : 0u, pm2 = prio ? (uint32_t)(93 * L / 100) : 0u;
+  if (exclusive_acc)
+    hipLaunchKernelGGL(k_accumulate<2>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
+                       w.offsets, B + 1, table, (uint32_t)L, w.raw29, pm1, pm2);
+  else
+    hipLaunchKernelGGL(k_accumulate<3>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
+                       w.offsets, B + 1, table, (uint32_t)L, w.raw29, pm1, pm2);
+  if (ev) hipEventRecord(ev[2], st);  // the accumulate phase is the k_accumulate launch alone
+  uint64_t stride = 1, cap = lcap;
+  for (int j = 0; j < CB_LEVELS; j++, stride *= CB_T) {
+    uint32_t* lin = w.chunklist + (uint64_t)j * lcap;
+    uint32_t* lout = j + 1 < CB_LEVELS ? w.chunklist + (uint64_t)(j + 1) * lcap : nullptr;
+    hipLaunchKernelGGL(k_combine_level, dim3(nb(cap)), dim3(256), 0, st, w.raw29, B + 1, w.segowner, w.offsets, lin,
+                       cnt + j, lout, lout ? cnt + j + 1 : nullptr, (uint32_t)L, stride);
+    cap = cap / CB_T + B + 16;
+  }
+  hipLaunchKernelGGL(k_combine, dim3(nb(COMBINE_LANES * (uint64_t)B)), dim3(256), 0, st, w.raw29, B + 1, w.offsets, B,
+                     (uint32_t)L, stride);
+}
+
 void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N,
              uint32_t* T_out, hipEvent_t* ev, uint64_t pbase, uint64_t pstride, bool exclusive_acc) {
   // ev (optional, 5 events): [0] start, [1] after digits+sort, [2] after k_accumulate,
@@ -1028,62 +1112,8 @@ void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* sc
     default:
       return;  // choose_c keeps 7 <= c <= KGS_C_MAX = 20
   }
-  // lo-pass grid: an upper bound of sum_p chunk_count(size_p) (blocks past cpre[NH] exit)
-  const uint64_t chunk_bound = std::min<uint64_t>((uint64_t)NH * SL_G, NH + N * (uint64_t)W / SL_CHUNK);
-  hipLaunchKernelGGL(k_lo_count, dim3((unsigned)chunk_bound), dim3(LC_THREADS), 0, st, w.locnt, w.lo, hi_off, cpre,
-                     bpart, NH, lob);
-  hipLaunchKernelGGL(k_lo_scatter, dim3((unsigned)chunk_bound), dim3(SL_THREADS), 0, st, w.sorted, w.offsets, w.locnt,
-                     (const uint32_t*)w.digit, w.lo, hi_off, cpre, bpart, NH, lob);
-  if (ev) hipEventRecord(ev[1], st);
-  const uint64_t E = N * (uint64_t)W;  // upper bound of nonzero entries
-  // one segment per resident thread (KGS_ACC_WAVES blocks of 256 per CU): every accumulate
-  // thread runs once and they all finish together (a second, partial round of blocks would
-  // leave most of the chip idle for a whole segment's duration)
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
-  }();
-  const uint64_t resident = (uint64_t)cus * KGS_ACC_WAVES * 256;
-  uint64_t L = (E + resident - 1) / resident;
-  if (L < 4) L = 4;
-  if ((E + L - 1) / L > (1ull << 18)) L = (E + (1ull << 18) - 1) >> 18;  // work buffers hold 2^18 + 2^16 segments
-  const uint64_t nseg = (E + L - 1) / L;
-  // chunk lists of the combine levels: list j holds <= nseg / CB_T^(j+1) + B entries
-  uint32_t* cnt = w.chunkcnt;
-  const uint64_t lcap = nseg / CB_T + B + 16;
-  hipMemsetAsync(cnt, 0, 4 * CB_LEVELS, st);
-  // progress priority (k_accumulate): KGS_ACC_PRIO 0 off, 1 the exclusive (two-lane) build, 2 every launch
-  static const int acc_prio = [] {
-    const char* e = getenv("KGS_ACC_PRIO");
-    return e ? atoi(e) : 1;
-  }();
-  // steps at 3/4 and 93/100 of the segment (a two-wave issue model with the leftover rate of the
-  // younger wave measured alone, 0.34 of the older's, puts these within 1 % of the best pair)
-#ifdef KGS_NO_PRIO_AUX
-  const bool prio = false;  // the A/B build without wave priorities: no step priority either
-  (void)acc_prio;
-#else
-  const bool prio = acc_prio >= 2 || (acc_prio == 1 && exclusive_acc);
-#endif
-  const uint32_t pm1 = prio ? (uint32_t)(3 * L / 4) : 0u, pm2 = prio ? (uint32_t)(93 * L / 100) : 0u;
-  if (exclusive_acc)
-    hipLaunchKernelGGL(k_accumulate<2>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
-                       w.offsets, B + 1, tb.table, (uint32_t)L, w.raw29, pm1, pm2);
-  else
-    hipLaunchKernelGGL(k_accumulate<3>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
-                       w.offsets, B + 1, tb.table, (uint32_t)L, w.raw29, pm1, pm2);
-  if (ev) hipEventRecord(ev[2], st);  // the accumulate phase is the k_accumulate launch alone
-  uint64_t stride = 1, cap = lcap;
-  for (int j = 0; j < CB_LEVELS; j++, stride *= CB_T) {
-    uint32_t* lin = w.chunklist + (uint64_t)j * lcap;
-    uint32_t* lout = j + 1 < CB_LEVELS ? w.chunklist + (uint64_t)(j + 1) * lcap : nullptr;
-    hipLaunchKernelGGL(k_combine_level, dim3(nb(cap)), dim3(256), 0, st, w.raw29, B + 1, w.segowner, w.offsets, lin,
-                       cnt + j, lout, lout ? cnt + j + 1 : nullptr, (uint32_t)L, stride);
-    cap = cap / CB_T + B + 16;
-  }
-  hipLaunchKernelGGL(k_combine, dim3(nb(COMBINE_LANES * (uint64_t)B)), dim3(256), 0, st, w.raw29, B + 1, w.offsets, B,
-                     (uint32_t)L, stride);
+  // E = N * W: upper bound of nonzero entries
+  msm_buckets(st, w, tb.table, N * (uint64_t)W, NH, lob, B, exclusive_acc, ev);
   if (ev) hipEventRecord(ev[3], st);
   // row / column sums (2^h + 2^l blocks), then the c bit sums
   const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
@@ -1096,6 +1126,159 @@ void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* sc
     hipLaunchKernelGGL(k_rowcol16, dim3((nlines * RC_LANES + 255) / 256), dim3(256), 0, st, w.part, w.raw29, c);
   hipLaunchKernelGGL(k_bitsum_rc, dim3(c), dim3(128), 0, st, T_out, w.part, w.raw29, c);
   if (ev) hipEventRecord(ev[4], st);
+}
+
+// ------------------------------------------------------------------ variable-base MSM (kgs_msm_points)
+// sum_i s_i P_i over ONE row of arbitrary points, without window tables. The window
+// moves from the table row into the sort key (sort_key<C, true>: j * B + |d|), so every window has a
+// bucket set of its own, records j * B + 1 .. j * B + B of raw29, and an entry's value is the point
+// index. Sort, accumulation and combine are the fixed-base kernels over W * B buckets (msm_buckets);
+// the tail below reduces each window's buckets to its c bit sums T_{j,k} = sum_{b has bit k} S_{j,b},
+// and the host finishes with sum_j 2^(c j) sum_k 2^k T_{j,k}: one Horner pass over the W * c points.
+//
+// The tail kernels are k_rowcol, k_rowcol16 and k_bitsum_rc with the window on blockIdx.y: window j
+// reads the records behind raw + RAW29_WORDS * j * B, writes its 2^h + 2^l line sums behind
+// rc + RAW29_WORDS * j * (2^h + 2^l) and its c points behind T + 32 * j * c.
+__global__ void __launch_bounds__(256) k_rowcol_win(uint32_t* __restrict__ rc, const uint32_t* __restrict__ raw, int c) {
+  KGS_AUX_PRIO();
+  __shared__ __attribute__((aligned(16))) uint32_t lds[128 * RAW29_WORDS];
+  const int l = c / 2, h = c - 1 - l;
+  const uint32_t r = blockIdx.x, t = threadIdx.x, win = blockIdx.y;
+  const uint32_t nlines = (1u << h) + (1u << l);
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  const bool row = r < (1u << h);
+  g1_acc29 v;
+  v.set_inf();
+  const uint32_t n = row ? 1u << l : 1u << h;  // elements of this row / column (<= 256 at c <= 16)
+  for (uint32_t e = t; e < n; e += 256) {
+    const uint32_t b = row ? (r << l) | e : (e << l) | (r - (1u << h));
+    if (b) v.add(g1_acc29::load_raw(run_rec(raw, b)));
+  }
+  v = block_tree_sum(v, lds);
+  if (t == 0) v.store_raw(rc + (uint64_t)RAW29_WORDS * (win * nlines + r));
+}
+
+__global__ void __launch_bounds__(256) k_rowcol16_win(uint32_t* __restrict__ rc, const uint32_t* __restrict__ raw,
+                                                      int c) {
+  KGS_AUX_PRIO();
+  const int l = c / 2, h = c - 1 - l;
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, win = blockIdx.y;
+  const uint32_t line = gid / RC_LANES, j = gid % RC_LANES;
+  const uint32_t nlines = (1u << h) + (1u << l);
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  const bool row = line < (1u << h);
+  const uint32_t n = row ? 1u << l : 1u << h;
+  g1_acc29 v;
+  v.set_inf();
+  if (line < nlines) {
+    for (uint32_t t = j; t < n; t += RC_LANES) {
+      const uint32_t b = row ? (line << l) | t : (t << l) | (line - (1u << h));
+      if (b) v.add(g1_acc29::load_raw(run_rec(raw, b)));
+    }
+  }
+#pragma unroll
+  for (int m = RC_LANES / 2; m >= 1; m >>= 1) v.add(shfl_xor_acc(v, m));  // every lane of the wave
+  if (line < nlines && j == 0) v.store_raw(rc + (uint64_t)RAW29_WORDS * (win * nlines + line));
+}
+
+__global__ void __launch_bounds__(128) k_bitsum_rc_win(uint32_t* __restrict__ T, const uint32_t* __restrict__ rc,
+                                                       const uint32_t* __restrict__ raw, int c) {
+  KGS_AUX_PRIO();
+  __shared__ __attribute__((aligned(16))) uint32_t lds[64 * RAW29_WORDS];
+  const int l = c / 2, h = c - 1 - l;
+  const int k = blockIdx.x;
+  const uint32_t t = threadIdx.x, win = blockIdx.y;
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  rc += (uint64_t)RAW29_WORDS * win * ((1u << h) + (1u << l));
+  g1_acc29 v;
+  v.set_inf();
+  if (k == c - 1) {
+    if (t == 0) v = g1_acc29::load_raw(run_rec(raw, 1u << (c - 1)));
+  } else {
+    const int bits = k < l ? l : h, j = k < l ? k : k - l;
+    const uint32_t base = k < l ? 1u << h : 0u;
+    for (uint32_t e = t; e < (1u << (bits - 1)); e += 128) {
+      const uint32_t idx = ((e >> j) << (j + 1)) | (1u << j) | (e & ((1u << j) - 1));
+      v.add(g1_acc29::load_raw(rc + (uint64_t)RAW29_WORDS * (base + idx)));
+    }
+  }
+  v = block_tree_sum(v, lds);
+  if (t == 0) v.to_xyzz().store(T + 32 * ((uint64_t)win * c + k));
+}
+
+// window of the sort that holds the variable-base key space [1, W * B]: 2^(c_sort - 1) >= W * B
+static int points_c_sort(int c) {
+  const uint64_t keys = (uint64_t)((255 + c - 1) / c) << (c - 1);
+  int lg = 0;
+  while ((1ull << lg) < keys) lg++;
+  return lg + 1 < 7 ? 7 : lg + 1;
+}
+
+MsmPointsSizes msm_points_sizes(uint64_t N, int c) {
+  MsmPointsSizes z;
+  const uint64_t W = (255 + c - 1) / c, E = N * W, keys = W << (c - 1);
+  const int cs = points_c_sort(c);
+  const uint64_t NH = (uint64_t)msm_nh(cs), bsort = 1ull << (cs - 1);
+  const uint64_t nblk = (N + 256 * SORT_SPT - 1) / (256 * SORT_SPT);
+  uint64_t nseg = (1ull << 18) + 2;  // msm_buckets: L >= 4 and at most 2^18 segments
+  if (E / 4 + 2 < nseg) nseg = E / 4 + 2;
+  z.digit = 4 * E;
+  z.sorted = 4 * E;  // also the N reduced scalars between the two sort passes (W >= 16 > 8 words each)
+  z.lo = E + 16;
+  z.blockhist = 4 * NH * (nblk + 1);
+  z.counts = 4 * (NH + 8);
+  z.offsets = 4 * (bsort + 4);  // the lo pass writes the offsets of all 2^(c_sort - 1) keys
+  z.cursor = 4 * (2 * ((uint64_t)NH_MAX + 8) + NH + E / SL_CHUNK + 64);
+  z.segowner = 4 * nseg;
+  z.locnt = 4 * bsort * SL_G;  // (partition, lo, chunk) counts
+  z.chunklist = 4 * CB_LEVELS * (nseg / CB_T + keys + 16);
+  z.raw29 = 4 * (uint64_t)RAW29_WORDS * (keys + 2 + nseg);
+  z.part = 4 * (uint64_t)RAW29_WORDS * W * ((1ull << (c - 1 - c / 2)) + (1ull << (c / 2)));
+  z.T = 128 * W * (uint64_t)c;
+  return z;
+}
+
+void msm_points_row29(hipStream_t st, uint32_t* row, uint64_t N) {
+  if (N) hipLaunchKernelGGL(k_tab_to29, dim3(nb(2 * N)), dim3(256), 0, st, row, 2 * N);
+}
+
+void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
+                    uint32_t* T_out) {
+  const int W = (255 + c - 1) / c;
+  const uint32_t B = (uint32_t)W << (c - 1);  // buckets of all windows
+  const int cs = points_c_sort(c);
+  const int lob = msm_lob(cs), NH = msm_nh(cs);
+  const uint32_t nblk = (uint32_t)((N + 256 * SORT_SPT - 1) / (256 * SORT_SPT));
+  uint32_t* ptot = w.counts;
+  uint32_t* hi_off = w.cursor;
+  uint32_t* cpre = w.cursor + NH_MAX + 8;
+  uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
+  uint32_t* bh = w.blockhist;
+  const size_t part_lds = (size_t)256 * SORT_SPT * W * 7 + (size_t)12 * NH;
+  uint32_t* scal_std = w.sorted;  // the reduced scalars, as in msm_run
+  switch (c) {
+#define KGS_SORT_C(CC)                                                                                               \
+  case CC:                                                                                                            \
+    hipLaunchKernelGGL((k_sort_hist<CC, true>), dim3(nblk), dim3(256), 0, st, bh, scalars_std, N, lob, NH, nblk,      \
+                       scal_std);                                                                                     \
+    hipLaunchKernelGGL(k_sort_scan_blocks, dim3(NH), dim3(256), 0, st, bh, ptot, nblk);                               \
+    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, st, hi_off, ptot, NH, w.offsets, B, cpre, bpart);          \
+    hipLaunchKernelGGL((k_sort_part<CC, true>), dim3(nblk), dim3(256), part_lds, st, (uint32_t*)w.digit, w.lo, bh,    \
+                       ptot, hi_off, scal_std, N, (uint64_t)0, (uint64_t)0, (uint64_t)0, lob, NH, nblk);              \
+    break;
+    KGS_SORT_C(7) KGS_SORT_C(8) KGS_SORT_C(9) KGS_SORT_C(10) KGS_SORT_C(11) KGS_SORT_C(12)
+    KGS_SORT_C(13) KGS_SORT_C(14) KGS_SORT_C(15) KGS_SORT_C(16)
+#undef KGS_SORT_C
+    default:
+      return;  // kgs_msm_points keeps MSM_POINTS_C_MIN <= c <= MSM_POINTS_C_MAX
+  }
+  msm_buckets(st, w, row29, N * (uint64_t)W, NH, lob, B, false, nullptr);
+  const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
+  if (!KGS_ROWCOL16)
+    hipLaunchKernelGGL(k_rowcol_win, dim3(nlines, W), dim3(256), 0, st, w.part, w.raw29, c);
+  else
+    hipLaunchKernelGGL(k_rowcol16_win, dim3((nlines * RC_LANES + 255) / 256, W), dim3(256), 0, st, w.part, w.raw29, c);
+  hipLaunchKernelGGL(k_bitsum_rc_win, dim3(c, W), dim3(128), 0, st, T_out, w.part, w.raw29, c);
 }
 
 // ------------------------------------------------------------------ fixed-base (synthetic SRS)

@@ -504,13 +504,7 @@ static void job_execute(napi_env, void* data) {
     if (prepare_prove(j)) group_execute(j);
     return;
   } else if (j->op == 4) {
-    const uint64_t n = j->scal.size() / 32;
-    int lg = 0;
-    while ((1ull << (lg + 1)) < n) lg++;
-    std::vector<uint8_t> mont(j->scal.size());
-    j->rc = kgs_srs_load_points(j->ctx, j->bases.data(), n, lg, lg);
-    if (j->rc == KGS_OK) j->rc = kgs_fr_to_mont(j->ctx, j->scal.data(), mont.data(), n);
-    if (j->rc == KGS_OK) j->rc = kgs_msm(j->ctx, mont.data(), n, j->msm_out);
+    j->rc = kgs_msm_points(j->ctx, j->bases.data(), j->scal.data(), j->scal.size() / 32, 0, j->msm_out);
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -1034,8 +1028,8 @@ static napi_value PairingEq(napi_env env, napi_callback_info info) {
 
 // msmPoints(ctx, bases, scalarsStd) -> Promise<64 B affine LEM sum_i s_i P_i> on the GPU of ctx (the
 // curve shim's G1.multiExpAffine, polynomial.js:1112, whose scalars are standard-form LE after
-// Fr.batchFromMontgomery): the bases become ctx's resident point set. Async work like every other
-// heavy call: the window-table build of the bases must not block the event loop.
+// Fr.batchFromMontgomery): kgs_msm_points reads the bases as given, builds no window tables and leaves
+// ctx's SRS alone. Async work like every other heavy call.
 static napi_value MsmPoints(napi_env env, napi_callback_info info) {
   size_t argc = 3;
   napi_value argv[3];
@@ -1046,9 +1040,9 @@ static napi_value MsmPoints(napi_env env, napi_callback_info info) {
   j->bases = bytes_of(env, argv[1]);
   j->scal = bytes_of(env, argv[2]);
   const uint64_t n = j->scal.size() / 32;
-  if (j->scal.size() % 32 || j->bases.size() != 64 * n || n < 2) {
+  if (j->scal.size() % 32 || j->bases.size() != 64 * n || n < 1) {
     delete j;
-    napi_throw_error(env, nullptr, "msmPoints: expected n >= 2 affine LEM bases and n 32 B scalars");
+    napi_throw_error(env, nullptr, "msmPoints: expected n >= 1 affine LEM bases and n 32 B scalars");
     return nullptr;
   }
   return queue(env, j, "kgs_msm_points");

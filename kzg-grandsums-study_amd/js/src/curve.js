@@ -12,7 +12,7 @@
 // Field elements are 32-byte little-endian Montgomery Uint8Arrays; G1 points are 96 B Jacobian
 // (x, y, z; z = 0 for the zero point) or 64 B affine (x, y; (0, 0) = zero), G2 points 192 B / 128 B
 // over Fq2 (c0, c1). Group arithmetic here is BigInt host plumbing (the verifier's handful of point
-// operations); G1.multiExpAffine runs on the GPU through the addon (kgs_msm over the given bases)
+// operations); G1.multiExpAffine runs on the GPU through the addon (kgs_msm_points over the given bases)
 // and curve.pairingEq through the native optimal-ate pairing (kgs_pairing_eq). The hot path itself
 // is libkgs's prover.
 const crypto = require("crypto");
@@ -207,7 +207,8 @@ function buildG1(F1, Fr, addon) {
         },
         // [ffjs] G1.multiExpAffine(bases, scalars): bases = n x 64 B affine LEM, scalars = n x 32 B
         // standard-form LE (the reference passes Fr.batchFromMontgomery(coef), polynomial.js:1112);
-        // returns a Jacobian point. Small inputs on the host, the rest on the GPU (kgs_msm).
+        // returns a Jacobian point. Small inputs on the host, the rest on the GPU (kgs_msm_points: a
+        // Pippenger over the bases as given, no window tables).
         multiExpAffine: async (bases, scalars) => {
             const n = Math.floor(scalars.byteLength / 32);
             if (bases.byteLength < 64 * n) throw new Error("multiExpAffine: not enough bases");
@@ -218,8 +219,8 @@ function buildG1(F1, Fr, addon) {
                 return encJ(R);
             }
             const a = addon();
-            // async on a libuv thread (the bases' window tables are built there, not on the event
-            // loop); the shim context's point set is per call, so its MSMs run one at a time
+            // async on a libuv thread. The library serialises the calls on the shim's context; the
+            // chain only keeps the promises resolving in call order
             const run = () => a.msmPoints(shimContext(a), bases.subarray(0, 64 * n), scalars.subarray(0, 32 * n));
             const p = shimBusy.then(run, run);
             shimBusy = p.catch(() => {});
@@ -229,7 +230,7 @@ function buildG1(F1, Fr, addon) {
     return G1;
 }
 
-// one context of its own for the shim's MSMs (its point set is replaced by every call)
+// one context of its own for the shim's MSMs (it never holds an SRS: the MSM takes its bases per call)
 let shimCtx = null;
 let shimBusy = Promise.resolve();
 function shimContext(a) {
