@@ -393,6 +393,34 @@ int kgs_fr_from_mont(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_std, u
 int kgs_fr_batch_inverse(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, uint64_t n);
 /* [ffjs] Fr.fft / Fr.ifft: natural order in and out, size 2^logm, ifft includes 1/m */
 int kgs_ntt(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logm, int inverse);
+/* The transforms as the provers launch them (a test primitive: the forward and inverse passes with their
+ * fused coset scalings, input length, orders and pass build). m = 2^logm, w = Fr.w[logm], g =
+ * KGS_NTT_COSET_GEN, rev = the bit reversal of logm-bit indices, NTT / INTT = kgs_ntt's forward /
+ * inverse (INTT with its 1/m). in_mont holds in_len elements (forward) or m elements (inverse), out_mont
+ * m elements.
+ *   forward (no KGS_NTT_INVERSE): in_len in 0 .. m; a_j = in[j] for j < in_len, 0 for in_len <= j < m
+ *     b_j = a_j g^j with KGS_NTT_COSET, else a_j                 A = NTT(b), A_k = sum_j b_j w^(jk)
+ *     out[k] = A_rev(k) with KGS_NTT_BITREV (the DIF's own order), else A_k
+ *   inverse (KGS_NTT_INVERSE): in_len is ignored
+ *     e_j = in[rev(j)] with KGS_NTT_BITREV (input in bit-reversed order), else in[j]
+ *     B = m INTT(e) with KGS_NTT_NO_SCALE (B_k = sum_j e_j w^(-jk)), else INTT(e)
+ *     out[k] = B_k g^-k with KGS_NTT_COSET, else B_k
+ *   KGS_NTT_INPLACE  the transform writes the device buffer it reads (same values)
+ *   KGS_NTT_INFLIGHT the pass build of one-lane (in-flight) contexts instead of the default one (same values)
+ * KGS_NTT_NO_SCALE means nothing to a forward call. The prover's launches: its coset evaluation of a
+ * polynomial is forward COSET | BITREV with in_len <= m; its quotient's return to coefficients inverse
+ * COSET | BITREV | NO_SCALE | INPLACE; the distributed prover's last pass inverse COSET; the reference
+ * replay forward with in_len < m; kgs_ntt flags 0 and KGS_NTT_INVERSE.
+ * KGS_E_ARG: logm outside 0 .. 28, a flag bit not listed here, a forward in_len > m, and inverse INPLACE
+ * without BITREV (that pass would gather bit-reversed addresses of the buffer it is writing). */
+#define KGS_NTT_COSET_GEN 5 /* the coset of every coset transform is g <w>, g = Fr's first non-residue */
+#define KGS_NTT_INVERSE 1
+#define KGS_NTT_COSET 2
+#define KGS_NTT_BITREV 4
+#define KGS_NTT_NO_SCALE 8
+#define KGS_NTT_INPLACE 16
+#define KGS_NTT_INFLIGHT 32
+int kgs_ntt_ex(kgs_ctx_t* ctx, const uint8_t* in_mont, uint64_t in_len, uint8_t* out_mont, int logm, int flags);
 /* [ffjs] G1.multiExpAffine(SRS[0..n), fromMont(scalars)) + toAffine (polynomial.js:1106-1115) */
 int kgs_msm(kgs_ctx_t* ctx, const uint8_t* scalars_mont, uint64_t n, uint8_t out_lem[64]);
 /* ComputeSGrandSumPolynomial / ComputeZGrandProductPolynomial evaluations before the ifft

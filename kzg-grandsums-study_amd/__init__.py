@@ -26,6 +26,8 @@ LIB_PATH = os.environ.get("KGS_LIB") or os.path.join(_HERE, "lib", "libkgs.so")
 GRANDSUM = 0
 GRANDPRODUCT = 1
 LOOKUP = 2
+# kgs_ntt_ex flags (include/kgs.h KGS_NTT_*)
+NTT_INVERSE, NTT_COSET, NTT_BITREV, NTT_NO_SCALE, NTT_INPLACE, NTT_INFLIGHT = 1, 2, 4, 8, 16, 32
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 FR_ONE_MONT = ((1 << 256) % R).to_bytes(32, "little")
@@ -119,6 +121,7 @@ def lib():
         L.kgs_fr_from_mont.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64]
         L.kgs_fr_batch_inverse.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64]
         L.kgs_ntt.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_int]
+        L.kgs_ntt_ex.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_int, ctypes.c_int]
         L.kgs_msm.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p]
         L.kgs_grand_build.argtypes = [ctypes.c_void_p, ctypes.c_int, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p,
                                       ctypes.c_uint64, c_u8p]
@@ -537,6 +540,17 @@ class Context:
         logm = m.bit_length() - 1
         out = ctypes.create_string_buffer(32 * m)
         _check(lib().kgs_ntt(self._h, _buf(data), out, logm, 1 if inverse else 0))
+        return out.raw
+
+    def ntt_ex(self, data, logm, flags=0):
+        """kgs_ntt_ex: the transforms as the provers launch them. data holds in_len = len(data) / 32
+        elements (forward: 0 .. 2^logm; inverse: 2^logm), flags is an OR of NTT_*; the result has
+        2^logm elements. include/kgs.h states each combination as a formula."""
+        in_len = len(data) // 32
+        if flags & NTT_INVERSE and 0 <= logm <= 28 and in_len != 1 << logm:
+            raise ValueError("an inverse transform takes 2^logm elements")
+        out = ctypes.create_string_buffer(32 << logm if 0 <= logm <= 28 else 32)
+        _check(lib().kgs_ntt_ex(self._h, _buf(data) if in_len else None, in_len, out, logm, flags))
         return out.raw
 
     def msm(self, scalars_mont):

@@ -119,7 +119,7 @@ void ensure_domain(kgs_ctx& c, int logM, bool twin) {
   auto d = std::make_shared<DomainTables>();
   d->device = c.device;
   // stage twiddle tables: tw[h + t] = w_{2h}^t for h = 2^l, l < logM (entries 1..M-1); coset powers
-  // g^i, g^-i (g = 5); 1/2^l for l <= logM
+  // g^i, g^-i (g = KGS_NTT_COSET_GEN); 1/2^l for l <= logM
   const size_t words = (size_t)8 * (4 * M + logM + 1);
   HC(dev_malloc((void**)&d->mem, 4 * words));
   d->tw_fwd = d->mem;
@@ -138,7 +138,7 @@ void ensure_domain(kgs_ctx& c, int logM, bool twin) {
     consts.push_back(w);
     consts.push_back(w.inverse());
   }
-  Fr g = Fr::from_u64(5);
+  Fr g = Fr::from_u64(KGS_NTT_COSET_GEN);
   consts.push_back(g);
   consts.push_back(g.inverse());
   uint32_t* dc = c.scal(consts.data(), (int)consts.size());
@@ -176,7 +176,7 @@ uint32_t* get_nxm1(kgs_ctx& c, int nbits, int lcs) {
   uint32_t* tmp = c.buf("nxm1_tmp", 32 * cs);
   // 1/(n (x - 1)) / cs: the coset inverse NTT of the quotient (coset_inv_prescaled) takes its 1/cs from here and
   // from the Z_H scalars of round 3 instead of a product per element
-  Fr consts[2] = {Fr::from_u64(5), Fr::from_u64(1ull << nbits) * Fr::from_u64(cs)};
+  Fr consts[2] = {Fr::from_u64(KGS_NTT_COSET_GEN), Fr::from_u64(1ull << nbits) * Fr::from_u64(cs)};
   uint32_t* d = c.scal(consts, 2);
   // w_M^j (j < M/2) is the last stage table, tw_fwd + 8 * (M/2)
   const uint64_t halfM = (1ull << c.logM) / 2;
@@ -1613,6 +1613,51 @@ int kgs_ntt(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logm,
   }
   check_launch();
   HC(hipMemcpyAsync(out_mont, b, 32 * m, hipMemcpyDeviceToHost, ctx->st));
+  ctx->sync();
+  API_END
+}
+
+// The provers' own launches of ntt_dif / ntt_dit (kgs.h): coset_fwd, coset_inv_prescaled, the distributed
+// prover's last pass (post and post_s together), the replay's short-input forward, under either pass build.
+int kgs_ntt_ex(kgs_ctx_t* ctx, const uint8_t* in_mont, uint64_t in_len, uint8_t* out_mont, int logm, int flags) {
+  API_BEGIN
+  if (!ctx) throw KgsError(KGS_E_ARG, "NULL ctx");
+  CTX_LOCK(ctx);
+  HC(hipSetDevice(ctx->device));
+  if (logm < 0 || logm > 28) throw KgsError(KGS_E_ARG, "bad logm");
+  const int known = KGS_NTT_INVERSE | KGS_NTT_COSET | KGS_NTT_BITREV | KGS_NTT_NO_SCALE | KGS_NTT_INPLACE |
+                    KGS_NTT_INFLIGHT;
+  if (flags & ~known) throw KgsError(KGS_E_ARG, "unknown NTT flag");
+  const bool inverse = flags & KGS_NTT_INVERSE, coset = flags & KGS_NTT_COSET, bitrev = flags & KGS_NTT_BITREV;
+  const bool inplace = flags & KGS_NTT_INPLACE;
+  const uint64_t m = 1ull << logm;
+  if (inverse && inplace && !bitrev)
+    throw KgsError(KGS_E_ARG, "an in-place inverse transform needs its input in bit-reversed order");
+  if (inverse) in_len = m;
+  if (in_len > m) throw KgsError(KGS_E_ARG, "input longer than the transform");
+  if (!out_mont || (in_len && !in_mont)) throw KgsError(KGS_E_ARG, "NULL argument");
+  if (logm > ctx->logM) ensure_domain(*ctx, logm);
+  uint32_t* a = ctx->buf("prim_a", 32 * m);
+  uint32_t* b = ctx->buf("prim_b", 32 * m);
+  ctx->reset_staging();
+  if (in_len) HC(hipMemcpyAsync(a, in_mont, 32 * in_len, hipMemcpyHostToDevice, ctx->st));
+  uint32_t* res = inplace ? a : b;
+  {
+    NttMode ntt_mode((flags & KGS_NTT_INFLIGHT) != 0);
+    if (inverse) {
+      ntt_dit(ctx->st, res, a, bitrev ? 1 : 0, logm, ctx->tw_inv, ctx->logM, coset ? ctx->coset_ipow : nullptr,
+              (flags & KGS_NTT_NO_SCALE) ? nullptr : ctx->invm + 8 * logm);
+    } else {
+      ntt_dif(ctx->st, res, a, in_len, logm, coset ? ctx->coset_pow : nullptr, ctx->tw_fwd, ctx->logM);
+      if (!bitrev) {
+        uint32_t* nat = inplace ? b : a;
+        launch_bitrev_copy(ctx->st, nat, res, logm);
+        res = nat;
+      }
+    }
+    check_launch();
+  }
+  HC(hipMemcpyAsync(out_mont, res, 32 * m, hipMemcpyDeviceToHost, ctx->st));
   ctx->sync();
   API_END
 }

@@ -302,7 +302,7 @@ struct Dist {
     if (it != c.dist_tabs.end()) return it->second;
     const uint64_t Ml = 1ull << logMl;
     uint32_t* t = c.buf(key, 32 * Ml);
-    Fr g5 = Fr::from_u64(5);
+    Fr g5 = Fr::from_u64(KGS_NTT_COSET_GEN);
     if (inverse) g5 = g5.inverse();
     Fr k[2] = {g5.pow_u64((uint64_t)W), g5.pow_u64((uint64_t)r)};
     uint32_t* d = c.scal(k, 2);
@@ -641,7 +641,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   } else {
     nxm1 = c.buf(nk, 32 * Mc);
     uint32_t* tmp = c.buf("d_nxm1_tmp", 32 * Mc);
-    Fr kk[2] = {Fr::from_u64(5), Fr::from_u64(n)};
+    Fr kk[2] = {Fr::from_u64(KGS_NTT_COSET_GEN), Fr::from_u64(n)};
     uint32_t* d = c.scal(kk, 2);
     launch_nxm1_e(c.st, tmp, c.tw_fwd, lcs, d, d + 8, W, r);
     launch_fr_batch_inv(c.st, nxm1, tmp, Mc);
@@ -659,7 +659,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   const Fr alpha = tr.challenge();
   const uint32_t rot = (uint32_t)(cs >> nbits);
   uint64_t qlen = (!gs && !sel) ? n - 1 : 2 * n - 2;  // deg Q + 1 bound
-  Fr gn = Fr::from_u64(5).pow_u64(n);
+  Fr gn = Fr::from_u64(KGS_NTT_COSET_GEN).pow_u64(n);
   // alpha_t: weight of the selT-binary term (none for a lookup, whose selT holds multiplicities)
   Fr qs[5] = {alpha, gamma, (gn - Fr::one()).inverse(), (gn.neg() - Fr::one()).inverse(), lk ? Fr::zero() : alpha};
   uint32_t* d_qs = c.scal(qs, 5);

@@ -330,7 +330,7 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   for (int j = 1; j < m; j++) dpow[j] = dpow[j - 1] * delta;
   const uint32_t rot = (uint32_t)(cs >> nbits);
   uint64_t qlen = all_gp_unsel ? n - 1 : 2 * n - 2;  // deg Q + 1 bound
-  const Fr gn = Fr::from_u64(5).pow_u64(n);
+  const Fr gn = Fr::from_u64(KGS_NTT_COSET_GEN).pow_u64(n);
   // 1/Z_H on the two coset halves, times 1/cs (the scaling of the inverse transform below; nxm1 carries it too)
   const Fr inv_cs = Fr::from_u64(cs).inverse();
   // One set of quotient scalars per argument: slot 4, the weight of the selT-binary term (none for a

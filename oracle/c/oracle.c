@@ -718,6 +718,31 @@ void orc_ntt(uint8_t* data_mont, uint64_t m, int inverse, int threads) {
   free(a);
 }
 
+/* data[j] *= base^j for j < m (Montgomery elements in place; base in standard form, 32 B LE): the coset
+ * scaling around orc_ntt in the checker of the GPU's coset transforms. Each thread starts its chunk at
+ * base^start by square-and-multiply and steps by one product per element. */
+void orc_scale_powers(uint8_t* data_mont, uint64_t m, const uint8_t base_std[32]) {
+  uint64_t bs[4];
+  memcpy(bs, base_std, 32);
+  const fe base = f_from_std(&FR, bs);
+  fe* a = (fe*)data_mont;
+  const uint64_t chunk = 4096;
+  const int64_t nchunks = (int64_t)((m + chunk - 1) / chunk);
+#pragma omp parallel for schedule(static)
+  for (int64_t c = 0; c < nchunks; c++) {
+    const uint64_t lo = (uint64_t)c * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    const uint64_t e[4] = {lo, 0, 0, 0};
+    fe p = f_pow(&FR, base, e);
+    for (uint64_t j = lo; j < hi; j++) {
+      fe x;
+      memcpy(x.v, a + j, 32);
+      x = RM(x, p);
+      memcpy(a + j, x.v, 32);
+      p = RM(p, base);
+    }
+  }
+}
+
 int orc_eval_evals_std(const uint8_t* evals_std, int nbits, const uint8_t x_std[32], uint8_t out_std[32]) {
   const uint64_t n = 1ull << nbits;
   uint64_t xs[4];

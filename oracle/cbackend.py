@@ -32,6 +32,8 @@ def lib():
         L.orc_keccak256.restype = None
         L.orc_ntt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int]
         L.orc_ntt.restype = None
+        L.orc_scale_powers.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+        L.orc_scale_powers.restype = None
         L.orc_eval_evals_std.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p]
         _lib = L
     return _lib
@@ -50,6 +52,14 @@ def ntt(data_mont, inverse=False, threads=0):
     """Natural-order NTT / inverse NTT of Montgomery-form bytes (oracle.c ntt)."""
     buf = ctypes.create_string_buffer(bytes(data_mont), len(data_mont))
     lib().orc_ntt(buf, len(data_mont) // 32, 1 if inverse else 0, threads)
+    return buf.raw[:len(data_mont)]
+
+
+def scale_powers(data_mont, base):
+    """data[j] * base^j (Montgomery-form bytes in and out; base a standard-form int): oracle.c
+    orc_scale_powers, the coset scaling around `ntt`."""
+    buf = ctypes.create_string_buffer(bytes(data_mont), len(data_mont))
+    lib().orc_scale_powers(buf, len(data_mont) // 32, int(base % bn.R).to_bytes(32, "little"))
     return buf.raw[:len(data_mont)]
 
 

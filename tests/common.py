@@ -40,6 +40,26 @@ def mont_bytes(vals):
     return b"".join(bn.fr_to_bytes(v) for v in vals)
 
 
+# the largest value below r whose seven low 32-bit limbs are all 0xffffffff
+LOW_ONES = (((R >> 224) - 1) << 224) | ((1 << 224) - 1)
+
+
+def ntt_extreme_input(kind, m):
+    """-> Montgomery bytes of an m-element vector at the edge of the field"""
+    if kind == "all":
+        return mont_bytes([R - 1] * m)
+    if kind == "alternating":
+        return mont_bytes([R - 1 if i % 2 == 0 else 0 for i in range(m)])
+    if kind == "first":
+        return mont_bytes([R - 1] + [0] * (m - 1))
+    if kind == "last":
+        return mont_bytes([0] * (m - 1) + [R - 1])
+    # raw Montgomery words (the bytes themselves, not the Montgomery form of these values)
+    words = {"raw_r-1": [R - 1], "raw_r-2": [R - 2], "raw_low_ones": [LOW_ONES],
+             "raw_cycle": [R - 1, R - 2, LOW_ONES]}[kind]
+    return b"".join(words[i % len(words)].to_bytes(32, "little") for i in range(m))
+
+
 def make_inputs(seed, nbits, npols, selected):
     """-> (list of F std-bytes, list of T std-bytes, selF mont-bytes|None, selT mont-bytes|None)"""
     rnd = random.Random(seed)

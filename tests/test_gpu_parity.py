@@ -78,9 +78,10 @@ def test_from_mont_and_batch_inverse(ctx9):
     assert ctx9.fr_from_mont(b"") == b"" and ctx9.fr_batch_inverse(b"") == b""
 
 
-# 0..10: radix-8/4/2 passes only; 11..17: LDS-staged passes of 6/5/4 stages (k_ntt_lds_pass<3,3>,
-# <3,2>, <2,2>) followed by radix-8/4/2 passes, in every combination (11 = 6+5, 13 = 6+6+1,
-# 14 = 6+6+2, 15 = 6+6+3, 16 = 6+6+4, 17 = 6+6+5)
+# 0..10: radix-8/4/2 passes only; 11..17: LDS passes only, two per transform, of 5 to 9 stages
+# (ntt.hip lds_plan: 11 = 6+5, 12 = 6+6, 13 = 6+7, 14 = 6+8, 15 = 6+9, 16 = 7+9, 17 = 8+9; the DIT runs
+# the same passes in reverse). kgs_ntt launches them without scalings on a full-length input, in the
+# default pass build; the provers' other launches are in test_gpu_ntt_variants.py
 @pytest.mark.parametrize("logm", list(range(0, 18)))
 def test_ntt(ctx9, logm):
     rnd = random.Random(logm)
@@ -89,24 +90,8 @@ def test_ntt(ctx9, logm):
     assert unmb(ctx9.ntt(common.mont_bytes(v), True)) == OP.ntt(v, True)
 
 
-# the largest value below r whose seven low 32-bit limbs are all 0xffffffff
-_LOW_ONES = (((R >> 224) - 1) << 224) | ((1 << 224) - 1)
-
-
-def _ntt_extreme_input(kind, m):
-    """-> Montgomery bytes of an m-element vector at the edge of the field"""
-    if kind == "all":
-        return common.mont_bytes([R - 1] * m)
-    if kind == "alternating":
-        return common.mont_bytes([R - 1 if i % 2 == 0 else 0 for i in range(m)])
-    if kind == "first":
-        return common.mont_bytes([R - 1] + [0] * (m - 1))
-    if kind == "last":
-        return common.mont_bytes([0] * (m - 1) + [R - 1])
-    # raw Montgomery words (the bytes themselves, not the Montgomery form of these values)
-    words = {"raw_r-1": [R - 1], "raw_r-2": [R - 2], "raw_low_ones": [_LOW_ONES],
-             "raw_cycle": [R - 1, R - 2, _LOW_ONES]}[kind]
-    return b"".join(words[i % len(words)].to_bytes(32, "little") for i in range(m))
+_LOW_ONES = common.LOW_ONES
+_ntt_extreme_input = common.ntt_extreme_input  # shared with test_gpu_ntt_variants.py
 
 
 # one size per pass plan listed above test_ntt. The lazy butterflies keep values in [0, 2r) and
@@ -349,6 +334,151 @@ def test_grand_builder(K, kind, sel, nbits):
         ctx.grand_build(kind, common.mont_bytes(f), common.mont_bytes(t2), bn.fr_to_bytes(g),
                         common.mont_bytes(sF) if sel else None, common.mont_bytes(sT) if sel else None)
     ctx.close()
+
+
+def _builder_ref(kind, f, t, sF, sT, g):
+    """kgs_grand_build's output for any n (grandsum.js:6-57, grandproduct.js:6-52 as a scan; the
+    oracle's _grandsum_S / _grandproduct_Z need a power of two for their ifft): row i's term
+    num_i * batchInverse(den)_i, where batchInverse(0) = 0, accumulated into out[(i + 1) mod n].
+    -> (out, closes)"""
+    n = len(f)
+    num, den = [], []
+    for i in range(n):
+        a, b = (f[i] + g) % R, (t[i] + g) % R
+        num.append((b * sF[i] - a * sT[i]) % R if kind == 0 else (sF[i] * (a - 1) + 1) % R)
+        den.append(a * b % R if kind == 0 else (sT[i] * (b - 1) + 1) % R)
+    inv = OP.batch_inverse(den)
+    out, acc = [0] * n, kind
+    for i in range(n):
+        acc = (acc + num[i] * inv[i]) % R if kind == 0 else acc * num[i] * inv[i] % R
+        out[(i + 1) % n] = acc
+    return out, out[0] == kind
+
+
+@pytest.fixture(scope="module")
+def bctx(K):
+    c = K.Context(0)
+    c.load_ptau(common.oracle_ptau(3))
+    yield c
+    c.close()
+
+
+def _build(ctx, kind, f, t, g, sF=None, sT=None):
+    return unmb(ctx.grand_build(kind, common.mont_bytes(f), common.mont_bytes(t), bn.fr_to_bytes(g),
+                                common.mont_bytes(sF) if sF else None, common.mont_bytes(sT) if sT else None))
+
+
+def test_builder_ref_matches_oracle():
+    # the scan above against the oracle's own builders where both apply (n a power of two)
+    rnd = random.Random(5)
+    n = 64
+    f = rv(rnd, n)
+    t = [f[-1]] + f[:-1]
+    g = rnd.randrange(R)
+    sF, sT = [1] * (n - 1) + [0], [0] + [1] * (n - 1)
+    for kind, fn in ((0, P._grandsum_S), (1, P._grandproduct_Z)):
+        for a, b in (([1] * n, [1] * n), (sF, sT)):
+            out, ok = _builder_ref(kind, f, t, a, b, g)
+            assert ok and out == OP.ntt(fn(f, t, a, b, g).coef, False)
+
+
+# n off the tile (2048 rows) and off the 8 rows of a thread: the i < n padding of the last tile and
+# the i + 1 == n wrap into out[0], in all four kernels
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("sel", [False, True])
+@pytest.mark.parametrize("n", [1, 2, 3, 7, 8, 9, 255, 2047, 2048, 2049, 4097, 3 * 2048 + 5])
+def test_grand_builder_ragged(K, bctx, kind, sel, n):
+    rnd = random.Random(n * 4 + kind * 2 + sel)
+    f = rv(rnd, n)
+    t = [f[-1]] + f[:-1]
+    g = rnd.randrange(R)
+    sF = [1] * (n - 1) + [0] if sel else None
+    sT = [0] + [1] * (n - 1) if sel else None
+    want, ok = _builder_ref(kind, f, t, sF or [1] * n, sT or [1] * n, g)
+    assert ok
+    assert _build(bctx, kind, f, t, g, sF, sT) == want
+    if n == 4097:  # not a multiset -> the reference's error, at a ragged n too
+        t2 = list(t)
+        t2[2049] = (t2[2049] + 1) % R
+        with pytest.raises(K.KgsError, match="not well calculated"):
+            _build(bctx, kind, f, t2, g, sF, sT)
+
+
+def _zero_den_inputs(n, U, sel, seed, live=False):
+    """A grand-sum input whose rows U have a zero denominator and still a zero term, so the sum
+    closes: outside U, T is a rotation of F. Selected: the rows of U are switched off (selF = selT =
+    0) and carry f = -gamma, t = -gamma or both in turn; with `live`, f = -gamma, selF = 1, selT = 0
+    instead: a numerator t + gamma != 0 over a zero denominator, whose term batchInverse(0) = 0 still
+    makes zero. Unselected: f = t = -gamma (numerator t - f = 0)."""
+    rnd = random.Random(seed)
+    g = rnd.randrange(R)
+    U = sorted(U)
+    inU = set(U)
+    rest = [i for i in range(n) if i not in inU]
+    f, t = rv(rnd, n), [0] * n
+    for k, i in enumerate(rest):
+        t[i] = f[rest[k - 1]]
+    sF = sT = None
+    if sel:
+        sF, sT = [1] * n, [1] * n
+    for k, i in enumerate(U):
+        if not sel:
+            f[i] = t[i] = (-g) % R
+            continue
+        t[i] = rnd.randrange(R)
+        sF[i], sT[i] = (1, 0) if live else (0, 0)
+        if live or k % 3 == 0:
+            f[i] = (-g) % R
+        elif k % 3 == 1:
+            t[i] = (-g) % R
+        else:
+            f[i] = t[i] = (-g) % R
+    return f, t, sF, sT, g
+
+
+# rows with a zero denominator: the thread-chunk edges (8 rows per thread), the tile edge (2048), the
+# first row and the row whose term lands in out[0]; a whole thread chunk (its product stays 1); a whole
+# tile (its product stays 1). gamma is a Fiat-Shamir challenge inside a proof, so only the primitive
+# reaches k_builder_tileprod's and k_builder_finish's is_zero branches.
+@pytest.mark.parametrize("mode", ["unselected", "selected", "selected-live"])
+@pytest.mark.parametrize("n", [4096, 4097])
+@pytest.mark.parametrize("which", ["edges", "chunk", "tile"])
+def test_grand_builder_zero_denominators(bctx, which, n, mode):
+    U = {"edges": [0, 7, 8, 2047, 2048, n - 1], "chunk": range(2064, 2072), "tile": range(2048, 4096)}[which]
+    f, t, sF, sT, g = _zero_den_inputs(n, U, mode != "unselected", n + len(mode), mode == "selected-live")
+    want, ok = _builder_ref(0, f, t, sF or [1] * n, sT or [1] * n, g)
+    assert ok and len(set(want)) > n - len(U) - 8  # a non-trivial S
+    if n == 4096:
+        assert want == OP.ntt(P._grandsum_S(f, t, sF or [1] * n, sT or [1] * n, g).coef, False)
+    assert _build(bctx, 0, f, t, g, sF, sT) == want
+
+
+@pytest.mark.parametrize("mode", ["unselected", "selected", "selected-live"])
+def test_grand_builder_every_denominator_zero(bctx, mode):
+    n = 16
+    f, t, sF, sT, g = _zero_den_inputs(n, range(n), mode != "unselected", 16, mode == "selected-live")
+    assert _builder_ref(0, f, t, sF or [1] * n, sT or [1] * n, g) == ([0] * n, True)
+    assert _build(bctx, 0, f, t, g, sF, sT) == [0] * n
+
+
+@pytest.mark.parametrize("n", [16, 4096])
+def test_grand_builder_zero_denominator_that_does_not_close(K, bctx, n):
+    """An unselected grand product with some t_i = -gamma: that row's factor is f_i' * batchInverse(0) =
+    0, Z is zero from there on and Z[0] != 1. The oracle and the library give the reference's error;
+    the context builds correctly afterwards."""
+    rnd = random.Random(n)
+    f = rv(rnd, n)
+    t = [f[-1]] + f[:-1]
+    g = rnd.randrange(R)
+    for i in (5, n - 1):
+        t2 = list(t)
+        t2[i] = (-g) % R
+        assert _builder_ref(1, f, t2, [1] * n, [1] * n, g)[1] is False
+        with pytest.raises(ValueError, match="The grand-product polynomial Z is not well calculated"):
+            P._grandproduct_Z(f, t2, [1] * n, [1] * n, g)
+        with pytest.raises(K.KgsError, match="The grand-product polynomial Z is not well calculated"):
+            _build(bctx, 1, f, t2, g)
+    assert _build(bctx, 1, f, t, g) == _builder_ref(1, f, t, [1] * n, [1] * n, g)[0]
 
 
 @pytest.mark.parametrize("L", [2, 3, 8, 2047, 2048, 2049, 6000, 70000])

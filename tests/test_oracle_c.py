@@ -33,6 +33,38 @@ def test_ntt_matches_python_oracle(logm):
         assert C.ntt(common.mont_bytes(v), inverse) == common.mont_bytes(OP.ntt(v, inverse))
 
 
+@pytest.mark.parametrize("m", [0, 1, 2, 63, 4096, 4097, 10000])
+def test_scale_powers_matches_python_oracle(m):
+    """oracle.c's orc_scale_powers (data[j] *= base^j; chunks of 4096 with their own starting power)
+    against Python integers, for the coset generator, its inverse, 0, 1 and r - 1."""
+    import ntt_cases as N
+    rnd = random.Random(m)
+    v = [rnd.randrange(bn.R) for _ in range(m)]
+    for base in (N.COSET_GEN, pow(N.COSET_GEN, bn.R - 2, bn.R), 0, 1, bn.R - 1, rnd.randrange(bn.R)):
+        want = [x * pow(base, j, bn.R) % bn.R for j, x in enumerate(v)]
+        assert C.scale_powers(common.mont_bytes(v), base) == common.mont_bytes(want), base
+
+
+def test_coset_reference_c_matches_python():
+    """The two references of kgs_ntt_ex (tests/ntt_cases.py) agree at 2^10 on every flag combination the
+    GPU tests use, with a full and a short forward input: the C one checks the GPU above 2^12."""
+    import ntt_cases as N
+    logm = 10
+    m = 1 << logm
+    x = N.random_elements(77, m)
+    assert N.COSET_GEN == bn.FR_NQR  # g <w> misses <w>: g is the field's non-residue
+    for flags in (0, N.BITREV, N.COSET, N.COSET | N.BITREV):
+        for in_len in (m, m // 2, 65, 0):
+            d = x[:32 * in_len]
+            assert N.ref_c(d, logm, flags) == common.mont_bytes(N.ref_py(N.unmont(d), logm, flags)), (flags, in_len)
+    for flags in (0, N.BITREV, N.NO_SCALE, N.COSET, N.COSET | N.BITREV, N.COSET | N.BITREV | N.NO_SCALE):
+        f = flags | N.INVERSE
+        assert N.ref_c(x, logm, f) == common.mont_bytes(N.ref_py(N.unmont(x), logm, f)), flags
+    # and the inverse undoes the forward in every order
+    for flags in (0, N.BITREV, N.COSET, N.COSET | N.BITREV):
+        assert N.ref_c(N.ref_c(x, logm, flags), logm, flags | N.INVERSE) == x
+
+
 def test_msm_closed_form():
     _, srs = C.load_srs_bytes(common.oracle_ptau(9))
     o = P.SRS(common.oracle_ptau(9), common.tau())
