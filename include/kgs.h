@@ -427,6 +427,63 @@ int kgs_msm(kgs_ctx_t* ctx, const uint8_t* scalars_mont, uint64_t n, uint8_t out
  * (grandsum.js:6-57, grandproduct.js:6-52): out = S (or Z) evaluations, natural order */
 int kgs_grand_build(kgs_ctx_t* ctx, int kind, const uint8_t* f_mont, const uint8_t* t_mont, const uint8_t* sel_f,
                     const uint8_t* sel_t, const uint8_t gamma_mont[32], uint64_t n, uint8_t* out_mont);
+/* ---- round 3 as the provers launch it (test primitives, like kgs_ntt_ex: the entry points below and the
+ * round engine call the same host functions, so the scalar set-up and the launch choice under test are
+ * the provers' own). Per point, with s = S(x), sw = S(w x), f, t, and sf, st the selector values
+ * (unselected: absent), every product in Fr:
+ *   core  = [selected: ((st - st^2) a_t + (sf - sf^2)) alpha, a_t = 0 for KGS_LOOKUP, alpha otherwise] +
+ *           grand-sum / lookup:  (sw - s)(f + gamma)(t + gamma) + (selected: st (f + gamma) - sf (t + gamma);
+ *                                                                 unselected: f - t)
+ *           grand-product:       sw dT - s dF,  dT = t + gamma, dF = f + gamma (unselected),
+ *                                dT = st (t + gamma - 1) + 1, dF = sf (f + gamma - 1) + 1 (selected)
+ *   l1op  = s (grand-sum / lookup), s - 1 (grand-product)
+ * The quotient numerator of an argument is N(x) = alpha core(x) + L1(x) l1op(x) (prover.js:233-286).
+ *
+ * kgs_quotient_ex: the quotient of `count` arguments on a coset, (sum_j delta^j N_j) / Z_H times 1/cs (the
+ * scaling of the inverse transform that follows it in the prover, KGS_NTT_NO_SCALE). n = 2^nbits,
+ * cs = 2^lcs, rot = cs / n, g = KGS_NTT_COSET_GEN, w_cs = Fr.w[lcs], rev = the bit reversal of lcs-bit
+ * indices. Every array holds cs elements indexed by p as the kernels read them (the order of a forward
+ * KGS_NTT_COSET | KGS_NTT_BITREV transform): i = rev(p), x_i = g w_cs^i, and S_j(w x_i) is S_j[p'] with
+ * p' = rev((i + rot) mod cs). The values are arbitrary field elements (no degree is assumed).
+ *   q_out[p] = (1/cs) [ alpha / (x_i^n - 1) * sum_j delta^j core_j(p)  +  1 / (n (x_i - 1)) * sum_j delta^j l1op_j(p) ]
+ * count == 1 runs the single proof's kernel (delta_mont is ignored, and may be NULL), or with
+ * KGS_QUOT_FUSED the multi-argument kernel on one argument (the same values); count > 1 runs the
+ * multi-argument kernel in groups of eight arguments, the later groups adding to q_out. The 1/(n (x - 1))
+ * table is the context's own, cached per (nbits, lcs). The domain tables grow on demand as for kgs_ntt_ex;
+ * no SRS is needed.
+ * KGS_E_ARG: nbits outside 1 .. 27, lcs other than nbits or nbits + 1, count outside 1 .. KGS_MAX_ARGS, a
+ * flag bit other than KGS_QUOT_FUSED, an unknown kind, a NULL array or scalar (sel_f and sel_t must be both
+ * NULL or both set, and KGS_LOOKUP needs them). */
+typedef struct {
+  int kind;                                 /* KGS_GRANDSUM | KGS_GRANDPRODUCT | KGS_LOOKUP */
+  const uint8_t *S, *F, *T, *sel_f, *sel_t; /* cs x 32 B Montgomery each */
+} kgs_quot_arg_t;
+#define KGS_QUOT_FUSED 1
+int kgs_quotient_ex(kgs_ctx_t* ctx, int nbits, int lcs, const kgs_quot_arg_t* args, int count,
+                    const uint8_t alpha_mont[32], const uint8_t gamma_mont[32], const uint8_t delta_mont[32], int flags,
+                    uint8_t* q_out);
+/* The divisibility check of round 3 (the test behind "Polynomial is not divisible"): *nonzero = 1 iff
+ * N(w^(gbase + i)) != 0 for some i < n, else 0, with
+ *   N(w^(gbase + i)) = alpha core(i) + (gbase + i == 0 ? l1op(i) : 0)        (L1 is 1 at w^0, 0 elsewhere on H)
+ * over n x 32 B Montgomery arrays in natural order, core(i) taking sw = S[i + 1] for i + 1 < n and
+ * sw = *s_next for i = n - 1 (s_next == NULL: S[0], the wrap of a whole domain). n is any value >= 1 (up
+ * to 2^28), not only a power of two: with s_next and gbase this is the check of one block of a larger
+ * domain, as the distributed prover runs it on a rank's block, here without a rank group.
+ * KGS_E_ARG: n outside 1 .. 2^28, an unknown kind, a NULL array, scalar or result, one selector without the
+ * other, KGS_LOOKUP without selectors. */
+int kgs_divcheck(kgs_ctx_t* ctx, int kind, uint64_t n, const uint8_t* S, const uint8_t* f, const uint8_t* t,
+                 const uint8_t* sel_f, const uint8_t* sel_t, const uint8_t alpha_mont[32], const uint8_t gamma_mont[32],
+                 const uint8_t* s_next, uint64_t gbase, int* nonzero);
+/* The provers' linear combination of vectors (round 2's beta combinations, round 5's opening numerators):
+ *   out[i] = sum over the k with i < lens[k] of coef_k srcs[k][i]  +  (i == 0 ? c0 : 0),   i < out_len
+ * srcs[k] holds lens[k] x 32 B Montgomery elements (lens[k] may exceed out_len, and may be 0 with
+ * srcs[k] == NULL); coefs_mont holds count x 32 B. Terms are taken 32 to a launch, the later launches
+ * re-reading out as their first source. Source pointers that are equal are one device buffer, as in the
+ * prover, where a polynomial can enter a combination more than once.
+ * KGS_E_ARG: count outside 0 .. 256, out_len outside 1 .. 2^28, a lens[k] above 2^28, a NULL pointer
+ * (srcs, lens and coefs_mont may be NULL when count == 0). */
+int kgs_lincomb(kgs_ctx_t* ctx, const uint8_t* const* srcs, const uint64_t* lens, const uint8_t* coefs_mont, int count,
+                const uint8_t c0_mont[32], uint64_t out_len, uint8_t* out_mont);
 /* Polynomial.evaluate (polynomial.js:228-238) */
 int kgs_poly_eval(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, const uint8_t x_mont[32],
                   uint8_t out_mont[32]);

@@ -71,6 +71,15 @@ class Arg(ctypes.Structure):
                 ("evals_t", ctypes.POINTER(ctypes.c_void_p)), ("sel_f", ctypes.c_void_p), ("sel_t", ctypes.c_void_p)]
 
 
+class QuotArg(ctypes.Structure):
+    """kgs_quot_arg_t (include/kgs.h)."""
+    _fields_ = [("kind", ctypes.c_int), ("S", ctypes.c_void_p), ("F", ctypes.c_void_p), ("T", ctypes.c_void_p),
+                ("sel_f", ctypes.c_void_p), ("sel_t", ctypes.c_void_p)]
+
+
+QUOT_FUSED = 1  # kgs_quotient_ex flag (include/kgs.h KGS_QUOT_FUSED)
+
+
 class RangeError(ValueError):
     """What the reference's JavaScript throws as a RangeError ("offset is out of bounds": its divZh on a
     zero quotient, polynomial.js:857,884) — raised in reference-quirks mode only (include/kgs.h
@@ -125,6 +134,12 @@ def lib():
         L.kgs_msm.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p]
         L.kgs_grand_build.argtypes = [ctypes.c_void_p, ctypes.c_int, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p,
                                       ctypes.c_uint64, c_u8p]
+        L.kgs_quotient_ex.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(QuotArg), ctypes.c_int,
+                                      c_u8p, c_u8p, c_u8p, ctypes.c_int, c_u8p]
+        L.kgs_divcheck.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p,
+                                   c_u8p, c_u8p, c_u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int)]
+        L.kgs_lincomb.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64),
+                                  c_u8p, ctypes.c_int, c_u8p, ctypes.c_uint64, c_u8p]
         L.kgs_poly_eval.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, c_u8p]
         L.kgs_poly_div_x_sub.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, c_u8p]
         L.kgs_lookup_multiplicities.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, PP, PP, c_u8p, c_u8p]
@@ -564,6 +579,60 @@ class Context:
         out = ctypes.create_string_buffer(32 * n)
         _check(lib().kgs_grand_build(self._h, kind, _buf(f_mont), _buf(t_mont), _buf(sel_f), _buf(sel_t),
                                      _buf(gamma_mont), n, out))
+        return out.raw
+
+    def quotient_ex(self, nbits, lcs, args, alpha_mont, gamma_mont, delta_mont=None, flags=0):
+        """kgs_quotient_ex: round 3's quotient launches on a coset of 2^lcs points. args is a list of
+        (kind, S, F, T, sel_f, sel_t): Montgomery buffers of 2^lcs elements in the kernels' (bit-reversed)
+        order, sel_f / sel_t None for an unselected argument. Returns q as 2^lcs elements; include/kgs.h
+        states it as a formula."""
+        shape_ok = 1 <= nbits <= 27 and lcs in (nbits, nbits + 1)  # else the library refuses before it reads
+        cs = 1 << lcs if shape_ok else 1
+        recs = (QuotArg * max(len(args), 1))()
+        keep = []
+        for j, (kind, *bufs) in enumerate(args):
+            ptrs = []
+            for b in bufs:
+                if shape_ok and b is not None and len(b) != 32 * cs:
+                    raise ValueError("every array holds 2^lcs 32-byte elements")
+                p, k = _ptr(b) if b is not None else (None, None)
+                ptrs.append(p)
+                keep.append(k)
+            recs[j] = QuotArg(kind, *ptrs)
+        out = ctypes.create_string_buffer(32 * cs)
+        _check(lib().kgs_quotient_ex(self._h, nbits, lcs, recs, len(args), _buf(alpha_mont), _buf(gamma_mont),
+                                     _buf(delta_mont), flags, out))
+        return out.raw
+
+    def divcheck(self, kind, S, f, t, alpha_mont, gamma_mont, sel_f=None, sel_t=None, s_next=None, gbase=0):
+        """kgs_divcheck: round 3's divisibility check over n = len(S) / 32 natural-order elements (any n);
+        s_next is S past the last element (None: S[0]), gbase the natural index of element 0. Returns 1
+        if the numerator is nonzero somewhere, else 0."""
+        n = len(S) // 32
+        if any(b is not None and len(b) != 32 * n for b in (f, t, sel_f, sel_t)):
+            raise ValueError("every array holds as many elements as S")
+        nz = ctypes.c_int(-1)
+        _check(lib().kgs_divcheck(self._h, kind, n, _buf(S), _buf(f), _buf(t), _buf(sel_f), _buf(sel_t), _buf(alpha_mont),
+                                  _buf(gamma_mont), _buf(s_next), gbase, ctypes.byref(nz)))
+        return nz.value
+
+    def lincomb(self, srcs, coefs_mont, c0_mont, out_len, lens=None):
+        """kgs_lincomb: out[i] = sum_k coef_k srcs[k][i] (i < lens[k]) + (i == 0 ? c0 : 0) through the
+        provers' run_lincomb. srcs: Montgomery buffers (the same object given twice is one buffer);
+        lens: elements of each (default: all of it); coefs_mont: len(srcs) x 32 B. Returns out_len elements."""
+        count = len(srcs)
+        lens = [len(s) // 32 for s in srcs] if lens is None else list(lens)
+        if len(lens) != count or len(coefs_mont) != 32 * count or any(32 * l > len(s) for s, l in zip(srcs, lens)):
+            raise ValueError("one length and one coefficient per source, no length beyond its buffer")
+        P = (ctypes.c_void_p * max(count, 1))()
+        seen = {}
+        for k, s in enumerate(srcs):
+            if id(s) not in seen:
+                seen[id(s)] = _ptr(s) if len(s) else (None, None)
+            P[k] = seen[id(s)][0]
+        L = (ctypes.c_uint64 * max(count, 1))(*lens)
+        out = ctypes.create_string_buffer(32 * out_len if 1 <= out_len <= 1 << 28 else 32)
+        _check(lib().kgs_lincomb(self._h, P, L, _buf(coefs_mont), count, _buf(c0_mont), out_len, out))
         return out.raw
 
     def poly_eval(self, coef_mont, x_mont):

@@ -468,6 +468,30 @@ struct LcTerms {
 };
 void run_lincomb(hipStream_t st, uint32_t* out, uint64_t n, const LcTerms& t);
 
+// Round 3's launch sequence (prover.cpp), shared by the round engine and the test primitives of kgs.h
+// (kgs_quotient_ex, kgs_divcheck). One argument's device vectors: on H in natural order for the
+// divisibility check (S, fcomb, tcomb, selectors), on the coset in bit-reversed order for the quotient.
+struct QuotIn {
+  int kind = 0;
+  const uint32_t *S = nullptr, *F = nullptr, *T = nullptr, *SF = nullptr, *ST = nullptr;  // SF, ST: nullptr unselected
+  bool gs() const { return kind != KGS_GRANDPRODUCT; }
+  bool lk() const { return kind == KGS_LOOKUP; }
+  bool sel() const { return SF != nullptr; }
+};
+// Stages the argument's nine quotient scalars (alpha, gamma, the two 1/Z_H / cs, alpha_t, the two alpha / Z_H
+// records) on the main stream and enqueues its divisibility check there: *flag |= 1 if some
+// N(w^(gbase + i)) != 0, i < n (poly.hip k_divcheck; S_next == nullptr: the wrap S[0]). Returns the staged
+// set, which run_quotient takes for argument 0. The check itself reads alpha, gamma and alpha_t only, so a
+// caller without a coset (kgs_divcheck) passes nbits = lcs = 0.
+const uint32_t* run_divcheck(kgs_ctx& c, int nbits, int lcs, const QuotIn& a, const Fr& alpha, const Fr& gamma, uint64_t n,
+                             uint32_t* flag, const uint32_t* S_next = nullptr, uint64_t gbase = 0);
+// Q = (sum_j dpow[j] N_j) / Z_H / cs on the coset of 2^lcs points, into Qc on the main stream: k_quotient
+// for one argument, with `fused` (the multi-argument prover, always) k_quotient_multi in groups of QM_MAX,
+// the later groups accumulating. qs0: argument 0's scalar set if run_divcheck has staged it (else it is
+// staged here). The 1/(n(x - 1)) table is get_nxm1's (a cache hit in a proof: round 2 has built it).
+void run_quotient(kgs_ctx& c, int nbits, int lcs, const std::vector<QuotIn>& args, const Fr& alpha, const Fr& gamma,
+                  const std::vector<Fr>& dpow, uint32_t* Qc, bool fused, const uint32_t* qs0 = nullptr);
+
 // ------------------------------------------------------------------ the protocol rounds (prover_rounds.cpp)
 enum R5Poly { R5_S, R5_Q, R5_F, R5_T, R5_SELF, R5_SELT, R5_POLT };
 

@@ -606,6 +606,65 @@ void run_lincomb(hipStream_t st, uint32_t* out, uint64_t n, const LcTerms& t) {
   } while (k < t.src.size());
 }
 
+// ------------------------------------------------------------------ round 3: divisibility and quotient
+// One set of quotient scalars per argument: slot 4, the weight of the selT-binary term (none for a
+// lookup, whose selT holds multiplicities), is the argument's own, the rest is shared; slots 2-3 are
+// 1/Z_H on the two coset halves times 1/cs (the scaling of the inverse transform that follows; nxm1
+// carries it too), slots 5-6 and 7-8 alpha / Z_H on each half as one 29-bit product record. The
+// divisibility checks and k_quotient read the argument's set, the fused kernel set 0.
+static const uint32_t* quot_scalars(kgs_ctx& c, int nbits, int lcs, bool lookup, const Fr& alpha, const Fr& gamma) {
+  const Fr gn = Fr::from_u64(KGS_NTT_COSET_GEN).pow_u64(1ull << nbits);
+  const Fr inv_cs = Fr::from_u64(1ull << lcs).inverse();
+  Fr qs[9] = {alpha, gamma, (gn - Fr::one()).inverse() * inv_cs, (gn.neg() - Fr::one()).inverse() * inv_cs,
+              lookup ? Fr::zero() : alpha};
+  fr29_record(alpha * qs[2], qs + 5);
+  fr29_record(alpha * qs[3], qs + 7);
+  return c.scal(qs, 9);
+}
+
+const uint32_t* run_divcheck(kgs_ctx& c, int nbits, int lcs, const QuotIn& a, const Fr& alpha, const Fr& gamma, uint64_t n,
+                             uint32_t* flag, const uint32_t* S_next, uint64_t gbase) {
+  const uint32_t* d_qs = quot_scalars(c, nbits, lcs, a.lk(), alpha, gamma);
+  launch_divcheck(c.st, !a.gs(), a.sel(), flag, a.S, a.F, a.T, a.SF, a.ST, d_qs, n, S_next, gbase);
+  return d_qs;
+}
+
+void run_quotient(kgs_ctx& c, int nbits, int lcs, const std::vector<QuotIn>& args, const Fr& alpha, const Fr& gamma,
+                  const std::vector<Fr>& dpow, uint32_t* Qc, bool fused, const uint32_t* qs0) {
+  const int m = (int)args.size();
+  const uint32_t rot = (uint32_t)((1ull << lcs) >> nbits);
+  const uint32_t* nxm1 = get_nxm1(c, nbits, lcs);
+  if (!qs0) qs0 = quot_scalars(c, nbits, lcs, args[0].lk(), alpha, gamma);
+  if (!fused) {  // the templated kernel of the single proof
+    if (m != 1) throw KgsError(KGS_E_ARG, "the single-argument quotient takes one argument");
+    launch_quotient(c.st, !args[0].gs(), args[0].sel(), Qc, args[0].S, args[0].F, args[0].T, args[0].SF, args[0].ST, nxm1,
+                    qs0, lcs, rot);
+    return;
+  }
+  for (int j0 = 0; j0 < m; j0 += QM_MAX) {
+    QuotMulti qm{};
+    qm.nargs = m - j0 < QM_MAX ? m - j0 : QM_MAX;
+    qm.accumulate = j0 > 0;
+    for (int i = 0; i < qm.nargs; i++) {
+      const int j = j0 + i;
+      QuotArg& q = qm.a[i];
+      q.S = args[j].S;
+      q.F = args[j].F;
+      q.T = args[j].T;
+      q.SF = args[j].SF;
+      q.ST = args[j].ST;
+      q.prod = !args[j].gs();
+      q.sel = args[j].sel();
+      q.lookup = args[j].lk();
+      dpow[j].to_bytes((uint8_t*)q.delta);
+      Fr rec[2];
+      fr29_record(dpow[j], rec);
+      memcpy(q.delta29, rec, 4 * LC_W29);
+    }
+    launch_quotient_multi(c.st, Qc, qm, nxm1, qs0, lcs, rot);
+  }
+}
+
 // Round 5 (prover.js:320-413): r(X) + the opening numerator as sum_k coef_k P_k + c0, from the
 // challenges and round-4 evaluations. Z_H(xi), L1(xi) as polynomial_utils.js:1-19. Shared by the
 // single-GPU and the distributed prover.
@@ -1751,6 +1810,126 @@ int kgs_grand_build(kgs_ctx_t* ctx, int kind, const uint8_t* f_mont, const uint8
   if (bad)
     throw KgsError(KGS_E_NOT_WELL_CALC, kind != KGS_GRANDPRODUCT ? "The grand-sum polynomial S is not well calculated"
                                                              : "The grand-product polynomial Z is not well calculated");
+  API_END
+}
+
+// Round 3 and the linear combinations as the provers launch them (kgs.h): host buffers around
+// run_quotient, run_divcheck and run_lincomb, the functions the round engine calls.
+static void check_quot_kind(int kind, const void* sel_f, const void* sel_t) {
+  if (kind != KGS_GRANDSUM && kind != KGS_GRANDPRODUCT && kind != KGS_LOOKUP) throw KgsError(KGS_E_ARG, "bad kind");
+  if ((sel_f == nullptr) != (sel_t == nullptr)) throw KgsError(KGS_E_ARG, "selectors must be both given or both NULL");
+  if (kind == KGS_LOOKUP && !sel_f) throw KgsError(KGS_E_ARG, "a lookup needs its selectors");
+}
+
+int kgs_quotient_ex(kgs_ctx_t* ctx, int nbits, int lcs, const kgs_quot_arg_t* args, int count,
+                    const uint8_t alpha_mont[32], const uint8_t gamma_mont[32], const uint8_t delta_mont[32], int flags,
+                    uint8_t* q_out) {
+  API_BEGIN
+  if (!ctx) throw KgsError(KGS_E_ARG, "NULL ctx");
+  CTX_LOCK(ctx);
+  HC(hipSetDevice(ctx->device));
+  if (nbits < 1 || nbits > 27) throw KgsError(KGS_E_ARG, "bad nbits");
+  if (lcs != nbits && lcs != nbits + 1) throw KgsError(KGS_E_ARG, "the coset has n or 2n points");
+  if (count < 1 || count > KGS_MAX_ARGS) throw KgsError(KGS_E_ARG, "bad argument count");
+  if (flags & ~KGS_QUOT_FUSED) throw KgsError(KGS_E_ARG, "unknown quotient flag");
+  if (!args || !alpha_mont || !gamma_mont || !q_out || (count > 1 && !delta_mont)) throw KgsError(KGS_E_ARG, "NULL argument");
+  for (int j = 0; j < count; j++) {
+    if (!args[j].S || !args[j].F || !args[j].T) throw KgsError(KGS_E_ARG, arg_prefix(j) + "NULL argument");
+    check_quot_kind(args[j].kind, args[j].sel_f, args[j].sel_t);
+  }
+  if (lcs > ctx->logM) ensure_domain(*ctx, lcs);
+  ctx->reset_staging();
+  const size_t E = (size_t)32 << lcs;
+  auto up = [&](int j, const char* what, const uint8_t* h) -> const uint32_t* {
+    if (!h) return nullptr;
+    uint32_t* d = ctx->buf("qx" + std::to_string(j) + "_" + what, E);
+    HC(hipMemcpyAsync(d, h, E, hipMemcpyHostToDevice, ctx->st));
+    return d;
+  };
+  std::vector<QuotIn> in(count);
+  for (int j = 0; j < count; j++) {
+    const kgs_quot_arg_t& a = args[j];
+    in[j] = QuotIn{a.kind, up(j, "S", a.S), up(j, "F", a.F), up(j, "T", a.T), up(j, "SF", a.sel_f), up(j, "ST", a.sel_t)};
+  }
+  std::vector<Fr> dpow(count, Fr::one());
+  for (int j = 1; j < count; j++) dpow[j] = dpow[j - 1] * Fr::from_bytes(delta_mont);
+  uint32_t* q = ctx->buf("qx_q", E);
+  run_quotient(*ctx, nbits, lcs, in, Fr::from_bytes(alpha_mont), Fr::from_bytes(gamma_mont), dpow, q,
+               count > 1 || (flags & KGS_QUOT_FUSED));
+  check_launch();
+  HC(hipMemcpyAsync(q_out, q, E, hipMemcpyDeviceToHost, ctx->st));
+  ctx->reset_staging();
+  API_END
+}
+
+int kgs_divcheck(kgs_ctx_t* ctx, int kind, uint64_t n, const uint8_t* S, const uint8_t* f, const uint8_t* t,
+                 const uint8_t* sel_f, const uint8_t* sel_t, const uint8_t alpha_mont[32], const uint8_t gamma_mont[32],
+                 const uint8_t* s_next, uint64_t gbase, int* nonzero) {
+  API_BEGIN
+  if (!ctx) throw KgsError(KGS_E_ARG, "NULL ctx");
+  CTX_LOCK(ctx);
+  HC(hipSetDevice(ctx->device));
+  if (n < 1 || n > (1ull << 28)) throw KgsError(KGS_E_ARG, "bad n");
+  if (!S || !f || !t || !alpha_mont || !gamma_mont || !nonzero) throw KgsError(KGS_E_ARG, "NULL argument");
+  check_quot_kind(kind, sel_f, sel_t);
+  ctx->reset_staging();
+  const size_t E = 32 * n;
+  auto up = [&](const char* name, const uint8_t* h, size_t extra) -> uint32_t* {
+    if (!h) return nullptr;
+    uint32_t* d = ctx->buf(name, E + extra);
+    HC(hipMemcpyAsync(d, h, E, hipMemcpyHostToDevice, ctx->st));
+    return d;
+  };
+  uint32_t* dS = up("dc_S", S, 32);  // S[n]: the continuation
+  if (s_next) HC(hipMemcpyAsync(dS + 8 * n, s_next, 32, hipMemcpyHostToDevice, ctx->st));
+  const QuotIn on_h{kind, dS, up("dc_f", f, 0), up("dc_t", t, 0), up("dc_sf", sel_f, 0), up("dc_st", sel_t, 0)};
+  uint32_t* flags = ctx->buf("flags", 64);
+  HC(hipMemsetAsync(flags, 0, 64, ctx->st));
+  run_divcheck(*ctx, 0, 0, on_h, Fr::from_bytes(alpha_mont), Fr::from_bytes(gamma_mont), n, flags,
+               s_next ? dS + 8 * n : nullptr, gbase);
+  check_launch();
+  uint32_t* hf = (uint32_t*)ctx->pin(64);
+  HC(hipMemcpyAsync(hf, flags, 64, hipMemcpyDeviceToHost, ctx->st));
+  ctx->sync();
+  *nonzero = hf[0] != 0;
+  ctx->reset_staging();
+  API_END
+}
+
+int kgs_lincomb(kgs_ctx_t* ctx, const uint8_t* const* srcs, const uint64_t* lens, const uint8_t* coefs_mont, int count,
+                const uint8_t c0_mont[32], uint64_t out_len, uint8_t* out_mont) {
+  API_BEGIN
+  if (!ctx) throw KgsError(KGS_E_ARG, "NULL ctx");
+  CTX_LOCK(ctx);
+  HC(hipSetDevice(ctx->device));
+  if (count < 0 || count > 256) throw KgsError(KGS_E_ARG, "bad term count");
+  if (out_len < 1 || out_len > (1ull << 28)) throw KgsError(KGS_E_ARG, "bad output length");
+  if (!c0_mont || !out_mont || (count && (!srcs || !lens || !coefs_mont))) throw KgsError(KGS_E_ARG, "NULL argument");
+  // equal host pointers share one device copy (of the longest length asked of them)
+  std::map<const uint8_t*, uint64_t> need;
+  for (int k = 0; k < count; k++) {
+    if (lens[k] > (1ull << 28)) throw KgsError(KGS_E_ARG, "bad term length");
+    if (lens[k] && !srcs[k]) throw KgsError(KGS_E_ARG, "NULL source");
+    if (lens[k]) need[srcs[k]] = std::max(need[srcs[k]], lens[k]);
+  }
+  uint64_t total = 0;
+  for (auto& kv : need) total += kv.second;
+  ctx->reset_staging();
+  uint32_t* pool = ctx->buf("lc_src", 32 * (total ? total : 1));
+  uint32_t* out = ctx->buf("lc_out", 32 * out_len);
+  std::map<const uint8_t*, const uint32_t*> dev;
+  uint64_t at = 0;
+  for (auto& kv : need) {
+    HC(hipMemcpyAsync(pool + 8 * at, kv.first, 32 * kv.second, hipMemcpyHostToDevice, ctx->st));
+    dev[kv.first] = pool + 8 * at;
+    at += kv.second;
+  }
+  LcTerms lt;
+  for (int k = 0; k < count; k++) lt.add(lens[k] ? dev[srcs[k]] : pool, lens[k], Fr::from_bytes(coefs_mont + 32 * k));
+  lt.c0 = Fr::from_bytes(c0_mont);
+  run_lincomb(ctx->st, out, out_len, lt);
+  HC(hipMemcpyAsync(out_mont, out, 32 * out_len, hipMemcpyDeviceToHost, ctx->st));
+  ctx->sync();
   API_END
 }
 

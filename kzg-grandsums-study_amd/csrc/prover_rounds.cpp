@@ -298,7 +298,7 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
     coset_fwd(c, s.cosS, s.Sc, n, lcs, s2);
     r2.push_back(commit_launch(c, s.Sc, n, slot++, j & 1));  // lane 1 follows the join: it sees Sc
   }
-  uint32_t* nxm1 = get_nxm1(c, nbits, lcs);
+  get_nxm1(c, nbits, lcs);  // built (first proof of this shape) under round 2's MSMs; run_quotient finds it cached
   check_launch();
   uint32_t* h_flags = (uint32_t*)c.pin(4 * FL_WORDS);
   HC(hipMemcpyAsync(h_flags, flags, 4 * FL_WORDS, hipMemcpyDeviceToHost, c.st));
@@ -328,53 +328,20 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   std::vector<Fr> dpow(m);
   dpow[0] = Fr::one();
   for (int j = 1; j < m; j++) dpow[j] = dpow[j - 1] * delta;
-  const uint32_t rot = (uint32_t)(cs >> nbits);
   uint64_t qlen = all_gp_unsel ? n - 1 : 2 * n - 2;  // deg Q + 1 bound
-  const Fr gn = Fr::from_u64(KGS_NTT_COSET_GEN).pow_u64(n);
-  // 1/Z_H on the two coset halves, times 1/cs (the scaling of the inverse transform below; nxm1 carries it too)
-  const Fr inv_cs = Fr::from_u64(cs).inverse();
-  // One set of quotient scalars per argument: slot 4, the weight of the selT-binary term (none for a
-  // lookup, whose selT holds multiplicities), is the argument's own, the rest is shared; slots 5-6 and
-  // 7-8 are alpha / Z_H on each coset half as one 29-bit product record. The divisibility checks and
-  // k_quotient read the argument's set, the fused kernel set 0.
-  uint32_t* d_qs0 = nullptr;
+  // every argument's divisibility check on H, then the one quotient on the coset (run_divcheck and
+  // run_quotient, prover.cpp: the scalar sets and the choice of kernel): k_quotient for the single proof,
+  // the fused kernel for several arguments
+  std::vector<QuotIn> qin(m);
+  const uint32_t* d_qs0 = nullptr;
   for (int j = 0; j < m; j++) {
-    Fr qs[9] = {alpha, gamma, (gn - Fr::one()).inverse() * inv_cs, (gn.neg() - Fr::one()).inverse() * inv_cs,
-                args[j].lk() ? Fr::zero() : alpha};
-    fr29_record(alpha * qs[2], qs + 5);
-    fr29_record(alpha * qs[3], qs + 7);
-    uint32_t* d_qs = c.scal(qs, 9);
+    const QuotIn on_h{args[j].kind, A[j].Sev, A[j].fcomb, A[j].tcomb, args[j].sel_f, args[j].sel_t};
+    const uint32_t* d_qs = run_divcheck(c, nbits, lcs, on_h, alpha, gamma, n, flags + FL_DIV + j);
     if (j == 0) d_qs0 = d_qs;
-    launch_divcheck(c.st, !args[j].gs(), args[j].sel(), flags + FL_DIV + j, A[j].Sev, A[j].fcomb, A[j].tcomb,
-                    args[j].sel_f, args[j].sel_t, d_qs, n);
+    qin[j] = QuotIn{args[j].kind, A[j].cosS, A[j].cosF, A[j].cosT, A[j].cosSF, A[j].cosST};
   }
   const uint32_t* Qc = c.buf("Qc", 32 * cs);
-  if (m == 1) {  // the templated kernel of the single proof
-    launch_quotient(c.st, !args[0].gs(), args[0].sel(), (uint32_t*)Qc, A[0].cosS, A[0].cosF, A[0].cosT, A[0].cosSF,
-                    A[0].cosST, nxm1, d_qs0, lcs, rot);
-  }
-  for (int j0 = 0; m > 1 && j0 < m; j0 += QM_MAX) {
-    QuotMulti qm{};
-    qm.nargs = m - j0 < QM_MAX ? m - j0 : QM_MAX;
-    qm.accumulate = j0 > 0;
-    for (int i = 0; i < qm.nargs; i++) {
-      const int j = j0 + i;
-      QuotArg& q = qm.a[i];
-      q.S = A[j].cosS;
-      q.F = A[j].cosF;
-      q.T = A[j].cosT;
-      q.SF = A[j].cosSF;
-      q.ST = A[j].cosST;
-      q.prod = !args[j].gs();
-      q.sel = args[j].sel();
-      q.lookup = args[j].lk();
-      dpow[j].to_bytes((uint8_t*)q.delta);
-      Fr rec[2];
-      fr29_record(dpow[j], rec);
-      memcpy(q.delta29, rec, 4 * LC_W29);
-    }
-    launch_quotient_multi(c.st, (uint32_t*)Qc, qm, nxm1, d_qs0, lcs, rot);
-  }
+  run_quotient(c, nbits, lcs, qin, alpha, gamma, dpow, (uint32_t*)Qc, m > 1, d_qs0);
   coset_inv_prescaled(c, (uint32_t*)Qc, Qc, lcs);
   check_launch();
   // latency mode: Q's 2n points over both MSM lanes (one lane's sort and tail overlap the other's
