@@ -194,6 +194,10 @@ int kgs_ptau_power(const char* path, int* power);
 int kgs_srs_load_points(kgs_ctx_t* ctx, const uint8_t* g1_lem, uint64_t npts, int power, int nbits_max);
 /* power of the loaded ptau, number of resident points, MSM window c */
 int kgs_srs_info(kgs_ctx_t* ctx, int* power, uint64_t* npts, int* window_c);
+/* *zero_points = 1 if some resident SRS point is the zero point (found when the window tables are
+ * built; such a table runs the bucket accumulation with its affine-infinity test), 0 if none is,
+ * -1 without an SRS */
+int kgs_srs_zero_points(kgs_ctx_t* ctx, int* zero_points);
 /* Read [tau]_2 (128 B LEM, section 3 offset 128) from a ptau (verifier input,
  * src/grandsum/mset_eq_kzg_verifier.js:18-19). */
 int kgs_ptau_read_tau_g2(const char* path, uint8_t out128[128]);
@@ -421,7 +425,8 @@ int kgs_ntt(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logm,
 #define KGS_NTT_INPLACE 16
 #define KGS_NTT_INFLIGHT 32
 int kgs_ntt_ex(kgs_ctx_t* ctx, const uint8_t* in_mont, uint64_t in_len, uint8_t* out_mont, int logm, int flags);
-/* [ffjs] G1.multiExpAffine(SRS[0..n), fromMont(scalars)) + toAffine (polynomial.js:1106-1115) */
+/* [ffjs] G1.multiExpAffine(SRS[0..n), fromMont(scalars)) + toAffine (polynomial.js:1106-1115).
+ * The scalars are canonical Montgomery forms (below r; any representative below 2^254 is taken). */
 int kgs_msm(kgs_ctx_t* ctx, const uint8_t* scalars_mont, uint64_t n, uint8_t out_lem[64]);
 /* ComputeSGrandSumPolynomial / ComputeZGrandProductPolynomial evaluations before the ifft
  * (grandsum.js:6-57, grandproduct.js:6-52): out = S (or Z) evaluations, natural order */

@@ -304,12 +304,17 @@ struct g1_acc29 {
   __device__ __forceinline__ void set_inf() { inf = true; }
 
   // this += (x, +-y): x, y = table coordinates (x*2^261 mod q, canonical, packed words);
-  // madd-2008-s with the same special cases as g1_xyzz::add_aff
+  // madd-2008-s with the same special cases as g1_xyzz::add_aff. ZP = false: the caller knows that
+  // (x, y) is never the zero point (a table built from an SRS without one), and the test of its 16
+  // words is compiled out.
+  template <bool ZP = true>
   __device__ __forceinline__ void add_aff(const uint32_t* xw, const uint32_t* yw, bool negy) {
-    uint32_t z = 0;
+    if (ZP) {
+      uint32_t z = 0;
 #pragma unroll
-    for (int i = 0; i < 8; i++) z |= xw[i] | yw[i];
-    if (z == 0) return;  // affine infinity
+      for (int i = 0; i < 8; i++) z |= xw[i] | yw[i];
+      if (z == 0) return;  // affine infinity
+    }
     const fq29 x2 = fq29::unpack(xw), y2 = fq29::unpack(yw);
     if (inf) {
       X = x2;

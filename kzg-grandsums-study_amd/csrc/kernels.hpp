@@ -43,6 +43,10 @@ struct MsmTables {
   uint32_t* table = nullptr;  // W x npts affine points (64 B)
   uint64_t npts = 0;
   int c = 0, W = 0;
+  // Row 0 holds 2^-256 * P_i (mod r), so that the digits are read off the scalars' Montgomery words
+  // (msm.hip scalar_digits). zero_points: some P_i is the zero point (found when the table is built);
+  // a table without one runs the bucket accumulation without the affine-infinity test.
+  bool zero_points = true;
 };
 
 constexpr int MSM_SL_G_MAX = 128;  // chunks per partition the lo-pass count buffer holds (msm.hip SL_G)
@@ -180,8 +184,10 @@ void launch_g1_fold(hipStream_t st, uint32_t* out_aff, const uint32_t* points, c
                     uint32_t* scratch);
 
 // msm.hip
+// table row 0: the points as loaded, replaced by rho * P_i (rho: standard form of 2^-256 mod r) before
+// the window rows are expanded; *zero_flag (a device word) ends as 1 if some P_i is the zero point
 void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int W, uint32_t* tmp_xyzz,
-                     uint32_t* scratch);
+                     uint32_t* scratch, const uint32_t rho[8], uint32_t* zero_flag);
 // scalars[i] multiplies SRS point pbase + pstride * i (pbase + pstride * (N - 1) < tb.npts).
 // exclusive_acc: the bucket accumulation takes a SIMD's whole register file at its two waves (for a
 // context whose two MSM lanes would otherwise co-run their accumulations and delay each other's

@@ -3,10 +3,12 @@
 //
 // Design (MI355X-first):
 //  * The SRS is fixed across proofs, so each base P_i is expanded ONCE into W = ceil(255/c)
-//    window copies 2^(c*j)·P_i (affine, 64 B, table[j][i]; 1.7-2 GB at n = 2^20 — HBM is 288 GB).
+//    window copies 2^(c*j)·rho·P_i, rho = 2^-256 mod r (affine, 64 B, table[j][i]; 1.7-2 GB at
+//    n = 2^20 — HBM is 288 GB).
 //    A commitment then needs a single set of B = 2^(c-1) signed-digit buckets shared by all
 //    windows: no per-window bucket reduction and no serial 2^c-doubling window combine.
-//  * scalars leave Montgomery form and are recoded into W signed c-bit digits (digit kernel);
+//  * the scalars' Montgomery words k_i 2^256 mod r are recoded as they are into W signed c-bit
+//    digits: the table holds 2^-256 P_i (scaled once, when it is built), so no scalar is converted;
 //  * counting sort of the N*W (digit -> point) entries by bucket (histogram, scan, scatter);
 //  * bucket accumulation over FIXED-SIZE segments of the sorted array (load balanced whatever
 //    the bucket sizes): one XYZZ mixed-add chain per segment, runs that straddle a segment
@@ -77,8 +79,45 @@ __global__ void __launch_bounds__(256) k_tab_to29(uint32_t* __restrict__ table, 
   (fq::load(table + 8 * i) * c).store(table + 8 * i);
 }
 
+// Row 0 as loaded -> rho * P_i for a constant 0 < rho < r (its words in the launch arguments: every
+// lane follows the same double-and-add schedule, from bit `top`, rho's highest set bit, down): XYZZ
+// out for k_batch_affine. A zero point stays zero and raises *zero_flag.
+struct MsmScalar {
+  uint32_t w[8];
+};
+__global__ void __launch_bounds__(256) k_tab_scale(uint32_t* __restrict__ tmp, const uint32_t* __restrict__ row0,
+                                                   uint64_t npts, MsmScalar rho, int top,
+                                                   uint32_t* __restrict__ zero_flag) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npts) return;
+  const g1_aff a = g1_aff::load(row0 + 16 * i);
+  if (a.is_inf()) *zero_flag = 1u;
+  g1_xyzz r = g1_xyzz::from_aff(a);
+  for (int k = top - 1; k >= 0; k--) {
+    r = r.dbl();
+    if ((rho.w[k >> 5] >> (k & 31)) & 1u) r.add_aff(a);
+  }
+  r.store(tmp + 32 * i);
+}
+
+// rho: the factor the fixed-base digits leave to the points (2^-256 mod r, standard form, from the
+// host field code: msm_run reads the digits off the scalars' Montgomery words). *zero_flag (device
+// word) ends as 1 when a row-0 point is the zero point (then so are its window copies), else 0.
 void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int W, uint32_t* tmp_xyzz,
-                     uint32_t* scratch) {
+                     uint32_t* scratch, const uint32_t rho[8], uint32_t* zero_flag) {
+  MsmScalar k;
+  int top = -1;
+  for (int b = 0; b < 8; b++) k.w[b] = rho[b];
+  for (int b = 0; b < 256; b++) {
+    if ((rho[b >> 5] >> (b & 31)) & 1u) top = b;
+  }
+  hipMemsetAsync(zero_flag, 0, 4, st);
+  if (top >= 0) {  // rho != 0
+    hipLaunchKernelGGL(k_tab_scale, dim3(nb(npts)), dim3(256), 0, st, tmp_xyzz, table, npts, k, top, zero_flag);
+    hipLaunchKernelGGL(k_batch_affine<32>, dim3(nb((npts + 31) / 32)), dim3(256), 0, st, table, tmp_xyzz, scratch,
+                       npts);
+  }
   for (int j = 1; j < W; j++) {
     const uint32_t* prev = table + (uint64_t)(j - 1) * npts * 16;
     uint32_t* cur = table + (uint64_t)j * npts * 16;
@@ -90,7 +129,7 @@ void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int 
 }
 
 // ------------------------------------------------------------------ digits + two-pass bucket sort
-// Entry (j, i) = (window, point) with signed digit d = digit_j(from_mont(scalar_i)); key |d| in
+// Entry (j, i) = (window, point) with signed digit d = digit_j(scalar_i's Montgomery words); key |d| in
 // [0, B], B = 2^(c-1); key 0 entries are dropped. Sort by key without global per-entry atomics:
 //  sorting is by k' = key - 1 in [0, B) (c - 1 bits): pass 1 partitions by p = k' >> LOB
 //          (NH = B >> LOB <= NH_MAX = 2048 partitions of 2^LOB <= 256 keys each; NH = 256 up to c = 17,
@@ -98,19 +137,27 @@ void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int 
 //          block x partition table is scanned; each block then counting-sorts its entries in LDS
 //          and writes them out as contiguous per-partition runs (coalesced stores instead of one
 //          scattered 4 B + 1 B store per entry). Digits are RECOMPUTED from the scalars in both
-//          passes instead of being materialised (one Montgomery product per scalar);
+//          passes instead of being materialised (shifts and masks of the words as they are);
 //  pass 2 sorts every partition by lo = key - (p << LOB) inside one workgroup, tile by tile
 //          through LDS (again run-wise stores), and writes the bucket offsets.
 // Order inside a bucket is unspecified (point addition is commutative).
-// digits of scalar i: from the Montgomery-form scalars (STD = false) or from their standard forms
-// (STD = true: k_sort_hist stores them for k_sort_part, which then skips the conversion). RED (the
-// variable-base MSM's histogram pass): the standard form is any 256-bit integer and is reduced mod r
-// first, by at most 5 conditional subtractions (2^256 / r < 6).
-template <int C, bool STD = false, bool RED = false>
+// digits of scalar i, read off its eight words as they are: the W signed windows of C bits are
+// sum_j d_j 2^(C j) = the 256-bit integer s at sc[8 i], for every s < 2^254: W C >= 255, so the top
+// window's bits are then below 2^(C-1) and it takes the carry from below without one of its own
+// (a larger s, up to 2^255 where W C > 255, would lose that carry).
+//  * Fixed base: sc holds the Montgomery words s = k R mod r (R = 2^256) every device vector already
+//    has, and the table holds R^-1 P_i (msm_build_table), so sum_i s_i (R^-1 P_i) = sum_i k_i P_i
+//    without a conversion per scalar. Any representative of s mod r in that range gives the same
+//    group element, because every G1 point has order r; the provers hand in canonical values
+//    below r < 2^254.
+//  * Variable base: sc holds standard forms. RED (its histogram pass): any 256-bit integer, reduced
+//    mod r first by at most 5 conditional subtractions (2^256 / r < 6) and stored to std_out for
+//    k_sort_part.
+template <int C, bool RED = false>
 __device__ __forceinline__ void scalar_digits(int32_t (&d)[(255 + C - 1) / C], const uint32_t* sc, uint64_t i,
                                               uint32_t* std_out = nullptr) {
   constexpr int W = (255 + C - 1) / C;
-  fr s = STD ? fr::load(sc + 8 * i) : fr::load(sc + 8 * i).from_mont();
+  fr s = fr::load(sc + 8 * i);
   if (RED) {
 #pragma unroll
     for (int k = 0; k < 5; k++) s = fr::reduce_once(s);
@@ -202,7 +249,8 @@ __device__ __forceinline__ uint32_t sort_key(int j, uint32_t m) {
 #endif
 constexpr int SORT_SPT = KGS_SORT_SPT;  // scalars per thread in the histogram / partition passes
 
-// VAR: the scalars are standard forms of any 256-bit integer (reduced here), keys by sort_key
+// VAR: the scalars are standard forms of any 256-bit integer (reduced here and stored to std_out),
+// keys by sort_key; fixed base: std_out is unused
 template <int C, bool VAR = false>
 __global__ void __launch_bounds__(256) k_sort_hist(uint32_t* __restrict__ bh, const uint32_t* __restrict__ sc,
                                                    uint64_t N, int lob, int NH, uint32_t nblk,
@@ -217,8 +265,8 @@ __global__ void __launch_bounds__(256) k_sort_hist(uint32_t* __restrict__ bh, co
     const uint64_t i = ((uint64_t)blockIdx.x * SORT_SPT + q) * 256 + threadIdx.x;
     if (i < N) {
       int32_t d[W];
-      if (VAR) scalar_digits<C, true, true>(d, sc, i, std_out);
-      else scalar_digits<C>(d, sc, i, std_out);
+      if (VAR) scalar_digits<C, true>(d, sc, i, std_out);
+      else scalar_digits<C>(d, sc, i);
 #pragma unroll
       for (int j = 0; j < W; j++) {
         if (d[j]) atomicAdd(&h[part_of(sort_key<C, VAR>(j, (uint32_t)(d[j] < 0 ? -d[j] : d[j])), lob)], 1u);
@@ -318,7 +366,7 @@ __global__ void __launch_bounds__(256) k_sort_part(uint32_t* __restrict__ tval, 
     const uint64_t i = ((uint64_t)blk * SORT_SPT + q) * 256 + tid;
     if (i < N) {
       int32_t d[W];
-      scalar_digits<C, true>(d, sc, i);  // sc: the standard forms k_sort_hist stored
+      scalar_digits<C>(d, sc, i);  // sc: the words k_sort_hist read (VAR: the reduced forms it stored)
       // entry values are 32-bit (point index | sign bit 31): the index arithmetic in 32 bits
       const uint32_t pidx = (uint32_t)pbase + (uint32_t)pstride * (uint32_t)i;
 #pragma unroll
@@ -686,7 +734,9 @@ constexpr int KGS_CLK_BLOCKS = 8192;
 __device__ unsigned long long g_kgs_clk[4 * KGS_CLK_BLOCKS];
 __device__ unsigned int g_kgs_clk_cu[KGS_CLK_BLOCKS];
 #endif
-template <int VW>
+// ZP: the table may hold zero points (MsmTables::zero_points; always for the variable-base row). A
+// table without them runs the add without the affine-infinity test of every gathered point.
+template <int VW, bool ZP>
 __global__ void __launch_bounds__(256, VW) k_accumulate(uint32_t* __restrict__ segowner,
                                                     uint32_t* __restrict__ chunklist, uint32_t* __restrict__ chunkcnt,
                                                     const uint32_t* __restrict__ sorted,
@@ -766,7 +816,7 @@ __global__ void __launch_bounds__(256, VW) k_accumulate(uint32_t* __restrict__ s
     bnext = offsets[b + 2 <= nbins ? b + 2 : nbins];
     const uint32_t xw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
     const uint32_t yw[8] = {a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
-    acc.add_aff(xw, yw, (v & 0x80000000u) != 0);
+    acc.add_aff<ZP>(xw, yw, (v & 0x80000000u) != 0);
     a0 = n0; a1 = n1; a2 = n2; a3 = n3;
     v = vn;
     vn = vnn;
@@ -1012,9 +1062,10 @@ __global__ void __launch_bounds__(128) k_bitsum_rc(uint32_t* __restrict__ T, con
 // The part of an MSM behind its partition pass, shared by the fixed-base driver (msm_run) and the
 // variable-base one (msm_points_run): the lo pass over NH partitions of 2^lob keys, the bucket
 // accumulation of the E (upper bound) sorted entries against the points at `table`, and the bucket
-// totals, which replace records 1 .. B of w.raw29. ev: msm_run's events [1] .. [2].
-static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, uint64_t E, int NH, int lob, uint32_t B,
-                        bool exclusive_acc, hipEvent_t* ev) {
+// totals, which replace records 1 .. B of w.raw29. zero_points: the points may include the zero point
+// (k_accumulate's ZP). ev: msm_run's events [1] .. [2].
+static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, bool zero_points, uint64_t E, int NH,
+                        int lob, uint32_t B, bool exclusive_acc, hipEvent_t* ev) {
   uint32_t* hi_off = w.cursor;
   uint32_t* cpre = w.cursor + NH_MAX + 8;
   uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
@@ -1056,12 +1107,17 @@ static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, uint6
   const bool prio = acc_prio >= 2 || (acc_prio == 1 && exclusive_acc);
 #endif
   const uint32_t pm1 = prio ? (uint32_t)(3 * L / 4) : 0u, pm2 = prio ? (uint32_t)(93 * L / 100) : 0u;
-  if (exclusive_acc)
-    hipLaunchKernelGGL(k_accumulate<2>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
-                       w.offsets, B + 1, table, (uint32_t)L, w.raw29, pm1, pm2);
-  else
-    hipLaunchKernelGGL(k_accumulate<3>, dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt, w.sorted,
-                       w.offsets, B + 1, table, (uint32_t)L, w.raw29, pm1, pm2);
+#define KGS_ACC(VW, ZP)                                                                                        \
+  hipLaunchKernelGGL((k_accumulate<VW, ZP>), dim3(nb(nseg)), dim3(256), 0, st, w.segowner, w.chunklist, cnt,   \
+                     w.sorted, w.offsets, B + 1, table, (uint32_t)L, w.raw29, pm1, pm2)
+  if (exclusive_acc) {
+    if (zero_points) KGS_ACC(2, true);
+    else KGS_ACC(2, false);
+  } else {
+    if (zero_points) KGS_ACC(3, true);
+    else KGS_ACC(3, false);
+  }
+#undef KGS_ACC
   if (ev) hipEventRecord(ev[2], st);  // the accumulate phase is the k_accumulate launch alone
   uint64_t stride = 1, cap = lcap;
   for (int j = 0; j < CB_LEVELS; j++, stride *= CB_T) {
@@ -1093,17 +1149,16 @@ void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* sc
   uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);  // lo-pass block -> partition
   uint32_t* bh = w.blockhist;                 // NH x nblk
   const size_t part_lds = (size_t)256 * SORT_SPT * W * 7 + (size_t)12 * NH;
-  // the scalars' standard forms (32 B each) go through w.sorted between the two sort passes: only the
-  // lo pass writes it later, and it holds E = N * W >= 8 N words (W >= 9 for c <= 31)
-  uint32_t* scal_std = w.sorted;
+  // both sort passes read the digits off the scalars' Montgomery words (scalar_digits)
   switch (c) {
 #define KGS_SORT_C(CC)                                                                                         \
   case CC:                                                                                                      \
-    hipLaunchKernelGGL(k_sort_hist<CC>, dim3(nblk), dim3(256), 0, st, bh, scalars, N, lob, NH, nblk, scal_std); \
+    hipLaunchKernelGGL(k_sort_hist<CC>, dim3(nblk), dim3(256), 0, st, bh, scalars, N, lob, NH, nblk,          \
+                       (uint32_t*)nullptr);                                                                     \
     hipLaunchKernelGGL(k_sort_scan_blocks, dim3(NH), dim3(256), 0, st, bh, ptot, nblk);                       \
     hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, st, hi_off, ptot, NH, w.offsets, B, cpre, bpart); \
     hipLaunchKernelGGL(k_sort_part<CC>, dim3(nblk), dim3(256), part_lds, st, (uint32_t*)w.digit, w.lo, bh,   \
-                       ptot, hi_off, scal_std, N, tb.npts, pbase, pstride, lob, NH, nblk);                    \
+                       ptot, hi_off, scalars, N, tb.npts, pbase, pstride, lob, NH, nblk);                     \
     break;
     KGS_SORT_C(7) KGS_SORT_C(8) KGS_SORT_C(9) KGS_SORT_C(10) KGS_SORT_C(11) KGS_SORT_C(12)
     KGS_SORT_C(13) KGS_SORT_C(14) KGS_SORT_C(15) KGS_SORT_C(16) KGS_SORT_C(17) KGS_SORT_C(18)
@@ -1113,7 +1168,7 @@ void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* sc
       return;  // choose_c keeps 7 <= c <= KGS_C_MAX = 20
   }
   // E = N * W: upper bound of nonzero entries
-  msm_buckets(st, w, tb.table, N * (uint64_t)W, NH, lob, B, exclusive_acc, ev);
+  msm_buckets(st, w, tb.table, tb.zero_points, N * (uint64_t)W, NH, lob, B, exclusive_acc, ev);
   if (ev) hipEventRecord(ev[3], st);
   // row / column sums (2^h + 2^l blocks), then the c bit sums
   const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
@@ -1255,7 +1310,9 @@ void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uin
   uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
   uint32_t* bh = w.blockhist;
   const size_t part_lds = (size_t)256 * SORT_SPT * W * 7 + (size_t)12 * NH;
-  uint32_t* scal_std = w.sorted;  // the reduced scalars, as in msm_run
+  // the reduced scalars (32 B each) go through w.sorted between the two sort passes: only the lo pass
+  // writes it later, and it holds E = N * W >= 8 N words
+  uint32_t* scal_std = w.sorted;
   switch (c) {
 #define KGS_SORT_C(CC)                                                                                               \
   case CC:                                                                                                            \
@@ -1272,7 +1329,7 @@ void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uin
     default:
       return;  // kgs_msm_points keeps MSM_POINTS_C_MIN <= c <= MSM_POINTS_C_MAX
   }
-  msm_buckets(st, w, row29, N * (uint64_t)W, NH, lob, B, false, nullptr);
+  msm_buckets(st, w, row29, true, N * (uint64_t)W, NH, lob, B, false, nullptr);
   const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
   if (!KGS_ROWCOL16)
     hipLaunchKernelGGL(k_rowcol_win, dim3(nlines, W), dim3(256), 0, st, w.part, w.raw29, c);

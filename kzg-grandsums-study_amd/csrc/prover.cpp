@@ -312,12 +312,23 @@ void load_points(kgs_ctx& c, const uint8_t* lem, uint64_t npts, int power, int n
       ~Tmp() {
         if (p) hipFree(p);
       }
-    } tmp, scr;
+    } tmp, scr, zflag;
     HC(dev_malloc(&tmp.p, npts * 128));
     HC(dev_malloc(&scr.p, npts * 32));
-    msm_build_table(c.st, t->tb.table, npts, cc, W, (uint32_t*)tmp.p, (uint32_t*)scr.p);
+    HC(dev_malloc(&zflag.p, 16));
+    // rho = 2^-256 mod r as a standard integer: the Montgomery word 1 stands for it
+    host::Fr rinv = host::Fr::zero();
+    rinv.v[0] = 1;
+    uint64_t rho64[4];
+    rinv.to_std(rho64);
+    uint32_t rho[8];
+    memcpy(rho, rho64, 32);
+    msm_build_table(c.st, t->tb.table, npts, cc, W, (uint32_t*)tmp.p, (uint32_t*)scr.p, rho, (uint32_t*)zflag.p);
     check_launch();
+    uint32_t zero_points = 1;
+    HC(hipMemcpyAsync(&zero_points, zflag.p, 4, hipMemcpyDeviceToHost, c.st));
     HC(hipStreamSynchronize(c.st));
+    t->tb.zero_points = zero_points != 0;
     std::lock_guard<std::mutex> lk(g_reg_mu);
     if (auto other = srs_lookup(c.device, file, nbits_max, srank, sworld)) {
       s = other;  // built concurrently by another context and published first: ours is released
@@ -929,6 +940,14 @@ int kgs_srs_info(kgs_ctx_t* ctx, int* power, uint64_t* npts, int* window_c) {
   if (power) *power = ctx->srs_power;
   if (npts) *npts = ctx->tb.npts;
   if (window_c) *window_c = ctx->tb.c;
+  API_END
+}
+
+int kgs_srs_zero_points(kgs_ctx_t* ctx, int* zero_points) {
+  API_BEGIN
+  if (!ctx || !zero_points) throw KgsError(KGS_E_ARG, "NULL argument");
+  CTX_LOCK(ctx);
+  *zero_points = ctx->srs ? (ctx->tb.zero_points ? 1 : 0) : -1;
   API_END
 }
 
