@@ -557,6 +557,49 @@ int kgs_msm_points(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* sca
  * points are copied into a buffer of the library's own before they are converted. */
 int kgs_msm_points_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t n,
                           int window_c, uint8_t out_lem[64]);
+/* [ffjs] G1.fft / G1.ifft: the radix-2 number-theoretic transform over G1 with the conventions of Fr.fft /
+ * Fr.ifft (kgs_ntt), natural order in and out:
+ *   forward  out_j = sum_i w^(i j) P_i            inverse  out_j = (1 / m) sum_i w^(-i j) P_i
+ * with m = 2^logm and w = Fr.w[logm], the root the Fr transform uses.
+ *   points_lem  m affine LEM points, 64 B each; 64 zero bytes is the identity, allowed anywhere. Points
+ *               are NOT validated (as for kgs_msm_points): a point off the curve or a coordinate >= q
+ *               gives an unspecified result, never a fault.
+ *   out_lem     m canonical affine LEM points (results compare byte for byte); may alias points_lem
+ *   logm        0 .. 24; logm == 0 copies the point
+ * ctx == NULL computes on the host (no GPU is touched). Failures: KGS_E_ARG for a logm out of range, a NULL
+ * buffer, a context attached to a rank group (kgs_ctx_set_group) or with MSM sharding on
+ * (kgs_ctx_set_shard). Same context contract as kgs_msm_points: the call holds the context's mutex, uses
+ * device buffers of its own (sized from m), needs no SRS and leaves the resident SRS, the domain tables
+ * and the prover's MSM work buffers as they are, and returns with nothing pending on the context's
+ * streams, on its error paths too (kgs_ctx_idle). */
+int kgs_g1_ntt(kgs_ctx_t* ctx, const uint8_t* points_lem, uint8_t* out_lem, int logm, int inverse);
+/* Same with device pointers (on ctx's device; ctx must not be NULL). The input is only read, unless the
+ * output aliases it, which is allowed. */
+int kgs_g1_ntt_device(kgs_ctx_t* ctx, const void* d_points_lem, void* d_out_lem, int logm, int inverse);
+/* The Lagrange-basis SRS [L_i(tau)]_1, i < 2^nbits, of the context's resident SRS: the inverse G1
+ * transform of its first 2^nbits points (what snarkjs' "prepare phase 2" computes), so that
+ * sum_i e_i [L_i(tau)]_1 commits to the polynomial with the evaluations e_i on the domain. The points are
+ * read from the resident window table's first row, which holds 2^-256 P_i: the factor 2^256 is folded into
+ * the inverse transform's final scaling (2^256 / n instead of 1 / n), so there is no extra pass over the
+ * points and no second read of the ptau file. The result is cached on the device per (SRS, nbits), shared
+ * by the contexts of that device, published once complete and released with the SRS tables; a second call
+ * returns the cached points without running the transform.
+ *   nbits    0 .. min(24, the nbits_max the SRS was loaded for)
+ *   out_lem  2^nbits affine LEM points, or NULL: build and cache only
+ * Failures: KGS_E_SRS "no SRS loaded"; KGS_E_ARG for an nbits out of range, a context attached to a rank
+ * group or with MSM sharding on, an SRS loaded as a slice (kgs_srs_load_ptau_slice). Context contract as
+ * for kgs_g1_ntt. */
+int kgs_srs_lagrange(kgs_ctx_t* ctx, int nbits, uint8_t* out_lem);
+/* Commitment from evaluations: out_lem = sum_i e_i [L_i(tau)]_1, i < 2^nbits, which is the point kgs_msm
+ * gives for the coefficient form of e (kgs_fr_to_mont, inverse kgs_ntt, kgs_msm), byte for byte, without
+ * computing the coefficients: the variable-base Pippenger of kgs_msm_points over the cached Lagrange
+ * bases (built on first use, kgs_srs_lagrange), which drops zero digits, so small evaluations stay cheap.
+ *   evals_std  2^nbits x 32 B little-endian STANDARD form; any 256-bit integer, taken mod r
+ *   out_lem    affine LEM; all-zero evaluations give 64 zero bytes
+ * Failures and context contract as for kgs_srs_lagrange; a NULL buffer is KGS_E_ARG. */
+int kgs_commit_evals(kgs_ctx_t* ctx, const uint8_t* evals_std, int nbits, uint8_t out_lem[64]);
+/* Same with a device pointer (on ctx's device), read only. */
+int kgs_commit_evals_device(kgs_ctx_t* ctx, const void* d_evals_std, int nbits, uint8_t out_lem[64]);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -570,6 +613,17 @@ int kgs_bench_msm_phases(kgs_ctx_t* ctx, const void* d_scalars_mont, uint64_t n,
                          uint64_t* entries);
 /* Run `reps` forward+inverse NTT pairs of size 2^logm on a device buffer; returns ms. */
 int kgs_bench_ntt(kgs_ctx_t* ctx, void* d_buf, int logm, int reps, double* ms);
+/* `reps` runs (after one warm-up) of a G1 transform leg of size 2^logm (1 .. 24) on device buffers, each
+ * between two events on ctx's stream: ms[r] = run r. what: 0 the forward transform, 1 the inverse, 2 the
+ * scaling pass alone (2^logm multiplications by one launch-uniform 254-bit constant and their affine
+ * conversion: the rate of a wave-uniform double-and-add, as k_tab_scale's). mapping: 0 the library's
+ * thread mapping, 1 one twiddle per lane, 2 one per wave wherever a stage has 64 groups. */
+int kgs_bench_g1_ntt(kgs_ctx_t* ctx, const void* d_in, void* d_out, int logm, int what, int mapping, int reps,
+                     double* ms);
+/* The route kgs_commit_evals_device replaces, with the same device-resident input: to Montgomery form,
+ * inverse NTT, kgs_msm over the resident window tables (profiles/g1_ntt_time.py times both by the wall
+ * clock; each ends synchronised). */
+int kgs_bench_coeff_commit(kgs_ctx_t* ctx, const void* d_evals_std, int nbits, uint8_t out_lem[64]);
 /* Host-only test hook of kgs_prove's staging copy (no GPU): copies len bytes src -> dst the way a
  * host input vector is staged (256 KiB pieces over the copy pool, spans of `span` bytes reported in
  * order once copied). spans_out[i] receives the byte offset of the i-th reported span (up to max);

@@ -171,6 +171,11 @@ def lib():
         L.kgs_msm_points.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p]
         L.kgs_msm_points_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
                                             ctypes.c_int, c_u8p]
+        L.kgs_g1_ntt.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_int]
+        L.kgs_g1_ntt_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.kgs_srs_lagrange.argtypes = [ctypes.c_void_p, ctypes.c_int, c_u8p]
+        L.kgs_commit_evals.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_int, c_u8p]
+        L.kgs_commit_evals_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.kgs_ctx_set_reference_quirks.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -704,6 +709,49 @@ class Context:
         64 B affine LEM sum."""
         out = ctypes.create_string_buffer(64)
         _check(lib().kgs_msm_points_device(self._h, d_points, d_scalars, n, window_c, out))
+        return out.raw
+
+    def g1_ntt(self, points_lem, inverse=False):
+        """G1.fft / G1.ifft on the GPU (kgs_g1_ntt): see the module-level g1_ntt."""
+        return _g1_ntt(self._h, points_lem, inverse)
+
+    def g1_ntt_device(self, d_in, d_out, logm, inverse=False):
+        """Device-resident twin (kgs_g1_ntt_device): d_in / d_out are device pointers (ints) to 2^logm
+        affine LEM points of 64 B; d_in is only read unless d_out is the same pointer, which is allowed."""
+        _check(lib().kgs_g1_ntt_device(self._h, d_in, d_out, logm, 1 if inverse else 0))
+
+    def srs_lagrange(self, nbits, fetch=True):
+        """The Lagrange-basis SRS [L_i(tau)]_1, i < 2^nbits, of the resident SRS (kgs_srs_lagrange), built
+        on the GPU on first use and cached on the device per (SRS, nbits). Returns 2^nbits x 64 B affine
+        LEM; fetch=False only builds and caches, and returns None."""
+        if not fetch:
+            _check(lib().kgs_srs_lagrange(self._h, nbits, None))
+            return None
+        out = ctypes.create_string_buffer(64 << nbits if 0 <= nbits <= 24 else 64)
+        _check(lib().kgs_srs_lagrange(self._h, nbits, out))
+        return out.raw
+
+    def commit_evals(self, evals_std, nbits=None):
+        """Commitment from evaluations (kgs_commit_evals): sum_i e_i [L_i(tau)]_1 over the resident SRS, the
+        bytes msm(ntt(fr_to_mont(e), inverse=True)) gives, without the coefficients. evals_std: 2^nbits
+        standard-form elements of 32 B, any 256-bit integers (nbits=None: from the length). Returns 64 B
+        affine LEM (zeros for the identity)."""
+        m = len(evals_std) // 32
+        if nbits is None:
+            nbits = m.bit_length() - 1
+        if len(evals_std) % 32 or not 0 <= nbits <= 24 or m != 1 << nbits:
+            raise ValueError("evals_std must hold 2^nbits 32-byte elements, nbits in 0 .. 24")
+        out = ctypes.create_string_buffer(64)
+        pe, ke = _ptr(evals_std)  # read in place
+        _check(lib().kgs_commit_evals(self._h, pe, nbits, out))
+        del ke
+        return out.raw
+
+    def commit_evals_device(self, d_evals, nbits):
+        """Device-resident twin (kgs_commit_evals_device): d_evals is a device pointer (int) to 2^nbits
+        standard-form elements, read only."""
+        out = ctypes.create_string_buffer(64)
+        _check(lib().kgs_commit_evals_device(self._h, d_evals, nbits, out))
         return out.raw
 
     def last_exchange(self):
@@ -1253,6 +1301,41 @@ def msm_points(points_lem, scalars_std, device=0, window_c=0):
     host."""
     handle = None if device is None else _context(device).handle
     return _msm_points(handle, points_lem, scalars_std, window_c)
+
+
+def _g1_ntt(handle, points_lem, inverse):
+    m = len(points_lem) // 64
+    if len(points_lem) % 64 or m == 0 or m & (m - 1):
+        raise ValueError("points_lem must hold a power of two of 64 B points")
+    out = ctypes.create_string_buffer(64 * m)
+    pp, kp = _ptr(points_lem)  # read in place
+    _check(lib().kgs_g1_ntt(handle, pp, out, m.bit_length() - 1, 1 if inverse else 0))
+    del kp
+    return out.raw
+
+
+def g1_ntt(points_lem, inverse=False, device=0):
+    """[ffjs] G1.fft / G1.ifft (kgs_g1_ntt): the number-theoretic transform over G1 of 2^logm affine LEM
+    points of 64 B (the zero point allowed, points are not validated), natural order in and out, with the
+    root Fr.w[logm] of the Fr transform: out_j = sum_i w^(ij) P_i, inverse out_j = (1/m) sum_i w^(-ij) P_i.
+    Returns 2^logm x 64 B canonical affine LEM. device=None computes on the host."""
+    handle = None if device is None else _context(device).handle
+    return _g1_ntt(handle, points_lem, inverse)
+
+
+def commit_evals(pTauFilename, evals, device=0):
+    """The commitment to the polynomial with the evaluations `evals` (standard-form Evaluations, or a
+    bytes-like of 2^nbits 32-byte elements) on the domain of their length, over the SRS of pTauFilename
+    (kgs_commit_evals): the Lagrange bases are built on first use and cached on the device. Returns 64 B
+    affine LEM."""
+    data = evals.eval if isinstance(evals, Evaluations) else evals
+    m = len(data) // 32
+    if len(data) % 32 or m == 0 or m & (m - 1):
+        raise ValueError("evals must hold a power of two of 32-byte elements")
+    nbits = m.bit_length() - 1
+    ctx = _context(device)
+    ctx.load_ptau(pTauFilename, nbits)
+    return ctx.commit_evals(data, nbits)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

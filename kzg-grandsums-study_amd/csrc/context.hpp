@@ -91,6 +91,20 @@ struct DBuf {
 // were loaded for) and the NTT / coset twiddle tables (the largest domain built so far serves every
 // smaller one: stage tables tw[h + t] = w_2h^t do not depend on the maximum domain). Published only
 // after their build has completed (stream synchronised), released when the last context drops them.
+// The Lagrange-basis SRS [L_i(tau)]_1, i < n, of a resident SRS (g1_ntt.cpp, kgs_srs_lagrange): one row in
+// the form msm_points_run reads
+struct LagrangeRow {
+  int device = 0;
+  uint32_t* row29 = nullptr;
+  uint64_t n = 0;
+  ~LagrangeRow() {
+    if (row29) {
+      hipSetDevice(device);
+      hipFree(row29);
+    }
+  }
+};
+
 struct SrsTables {
   int device = 0;
   std::string file;  // file identity (path + size + mtime) or "mem#<id>"
@@ -99,6 +113,9 @@ struct SrsTables {
   // slice_world * j only (slice_world == 1: the whole prefix)
   int slice_rank = 0, slice_world = 1;
   MsmTables tb;
+  // nbits -> the Lagrange bases of the first 2^nbits points; read and published under g_reg_mu, built
+  // outside it and published complete, released with the tables
+  std::map<int, std::shared_ptr<LagrangeRow>> lagrange;
   ~SrsTables() {
     if (tb.table) {
       hipSetDevice(device);
@@ -439,6 +456,11 @@ void commits_finish(kgs_ctx& c, const std::vector<Commit>& cms, std::vector<uint
 void commits_finish_with(kgs_ctx& c, const std::vector<Commit>& cms, std::vector<uint8_t*> outs, int world,
                          const HostAllgather& ag);
 void commit_finish(kgs_ctx& c, const Commit& cm, uint8_t out[64]);
+// The variable-base MSM over a row already in msm_points_run's form (msm_points.cpp): n >= 1 device
+// scalars in standard form, window_c as for kgs_msm_points, the call's own "mp_*" buffers, the host
+// finish. Ends with the main stream drained.
+void msm_points_over_row(kgs_ctx& c, const uint32_t* row29, const uint32_t* d_scalars_std, uint64_t n, int window_c,
+                         uint8_t out[64]);
 
 // Horner evaluations (tile partials on the device, tile combine on the host)
 struct EvalJob {

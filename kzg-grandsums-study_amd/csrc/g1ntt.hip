@@ -1,0 +1,225 @@
+// Number-theoretic transform over G1 for gfx950 — [ffjs] `G1.fft` / `G1.ifft` (kgs.h kgs_g1_ntt; DESIGN.md §18;
+// the entry points and the Lagrange-basis cache are in g1_ntt.cpp).
+//
+// Radix-2 decimation in time, natural order in and out: the first stage gathers its operands
+// bit-reversed from the input, stage `h` (half-width 1, 2, .., n/2) computes
+//   (a, b) -> (a + w b, a - w b),  w = omega_{2h}^t = omega_n^{t n / 2h},  t < h
+// on the pairs (g 2h + t, g 2h + t + h) of its G = n / 2h groups. A butterfly is one 254-bit scalar
+// multiplication and two additions for 256 B of traffic, so the stages are plain global-memory kernels,
+// one butterfly per thread; all the time is in the (n/2) log2 n twiddle multiplications.
+//   * The points are affine between the stages (launch_batch_affine after every stage: ~20 field
+//     products per point against ~3000 per butterfly): the multiplication then adds an affine b
+//     (madd, 10 products) instead of an XYZZ one (14), and so do the two additions to the affine a.
+//   * The twiddles are signed digits (NAF, digits of 3k - k): a third of the bits carry an addition
+//     instead of half. A record is 16 words, the masks of the +1 and of the -1 digits, built once per
+//     call by k_g1ntt_twiddles; the double-and-add loop negates b's y for a -1.
+//   * Twiddle index 0 (every stage; all of stage h = 1) is a copy, not a multiplication. With t < h no
+//     twiddle is omega^(n/2) = -1: that negation is the `a - w b` output.
+//   * Thread mapping. Per lane: thread i -> (g, t) = (i / h, i % h), adjacent lanes adjacent points, 64
+//     twiddles per wave: the `if (digit) add` diverges and every lane pays every addition. Per wave:
+//     (t, g) = (i / G, i % G), possible when G >= 64: the wave's 64 butterflies share t, the digits sit in
+//     scalar registers and the schedule is uniform, as k_tab_scale's is for rho (msm.hip).
+//   * The inverse transform's 1/n (kgs_srs_lagrange: 2^256 / n, which also takes rho = 2^-256 off the
+//     table row) is one more multiplication per point by a launch-uniform constant, k_g1ntt_scale.
+#include "kernels.hpp"
+
+namespace kgs {
+
+static inline unsigned nb(uint64_t work, unsigned bs = 256) { return (unsigned)((work + bs - 1) / bs); }
+
+struct G1NttWords {
+  uint32_t w[8];
+};
+
+// the NAF of k < 2^254 as two masks: digit i is +1 if bit i of pos, -1 if bit i of neg (i <= 254)
+__device__ __forceinline__ void naf_record(const uint32_t k[8], uint32_t* __restrict__ rec) {
+  uint32_t k3[8];
+  uint32_t carry = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {  // 3k = 2k + k
+    const uint32_t two = (k[i] << 1) | (i ? k[i - 1] >> 31 : 0u);
+    const uint64_t s = (uint64_t)two + k[i] + carry;
+    k3[i] = (uint32_t)s;
+    carry = (uint32_t)(s >> 32);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t p = k3[i] & ~k[i], n = k[i] & ~k3[i];
+    const uint32_t pn = i < 7 ? k3[i + 1] & ~k[i + 1] : 0u, nn = i < 7 ? k[i + 1] & ~k3[i + 1] : 0u;
+    rec[i] = (p >> 1) | (pn << 31);
+    rec[8 + i] = (n >> 1) | (nn << 31);
+  }
+}
+
+// rec[i] = NAF record of the standard form of root^i, i < count; rec[count] = that of `scale`
+// (standard form, < r). root: Montgomery words.
+__global__ void __launch_bounds__(256) k_g1ntt_twiddles(uint32_t* __restrict__ rec, uint64_t count, G1NttWords root,
+                                                        G1NttWords scale) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > count) return;
+  uint32_t k[8];
+  if (i == count) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) k[j] = scale.w[j];
+  } else {
+    fr b, x = fr::one();
+#pragma unroll
+    for (int j = 0; j < 8; j++) b.v[j] = root.w[j];
+    for (uint64_t e = i; e; e >>= 1) {
+      if (e & 1) x = x * b;
+      b = b.sqr();
+    }
+    x = x.from_mont();
+#pragma unroll
+    for (int j = 0; j < 8; j++) k[j] = x.v[j];
+  }
+  naf_record(k, rec + G1NTT_TW_WORDS * i);
+}
+
+// k * b for the record at rec. UNI: the record is the same for the whole wave.
+template <bool UNI>
+__device__ __forceinline__ g1_xyzz g1ntt_mul(const g1_aff& b, const uint32_t* __restrict__ rec) {
+  g1_xyzz r = g1_xyzz::inf();
+  if (b.is_inf()) return r;
+#pragma unroll 1
+  for (int w = 7; w >= 0; w--) {
+    uint32_t p = rec[w], n = rec[8 + w];
+    if (UNI) {
+      p = __builtin_amdgcn_readfirstlane(p);
+      n = __builtin_amdgcn_readfirstlane(n);
+    }
+#pragma unroll 1
+    for (int k = 31; k >= 0; k--) {
+      r = r.dbl();
+      const uint32_t m = 1u << k;
+      if ((p | n) & m) {
+        g1_aff s = b;
+        if (n & m) s.y = s.y.neg();
+        r.add_aff(s);
+      }
+    }
+  }
+  return r;
+}
+
+// One stage: out_xyzz[pa], out_xyzz[pb] = a + w b, a - w b. half_n = n / 2 butterflies, h = 2^logh.
+// bitrev_in: the operands are read from in_aff at the bit-reversed positions (the first stage).
+template <bool UNI>
+__global__ void __launch_bounds__(64) k_g1ntt_stage(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
+                                                    const uint32_t* __restrict__ tw, uint64_t half_n, int logh, int logn,
+                                                    int bitrev_in) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= half_n) return;
+  const int logG = logn - 1 - logh;
+  uint32_t t, g;
+  if (UNI) {  // logG >= 6 and 64-thread blocks: one t per wave
+    t = __builtin_amdgcn_readfirstlane((uint32_t)(i >> logG));
+    g = (uint32_t)i & ((1u << logG) - 1u);
+  } else {
+    g = (uint32_t)(i >> logh);
+    t = (uint32_t)i & ((1u << logh) - 1u);
+  }
+  const uint64_t pa = ((uint64_t)g << (logh + 1)) + t, pb = pa + ((uint64_t)1 << logh);
+  uint64_t sa = pa, sb = pb;
+  if (bitrev_in) {
+    sa = __brev((uint32_t)pa) >> (32 - logn);
+    sb = __brev((uint32_t)pb) >> (32 - logn);
+  }
+  const g1_aff a = g1_aff::load(in_aff + 16 * sa), b = g1_aff::load(in_aff + 16 * sb);
+  g1_xyzz T;
+  if (t == 0)
+    T = g1_xyzz::from_aff(b);
+  else
+    T = g1ntt_mul<UNI>(b, tw + G1NTT_TW_WORDS * ((uint64_t)t << logG));
+  g1_xyzz U = T;
+  U.Y = U.Y.neg();
+  T.add_aff(a);
+  U.add_aff(a);
+  T.store(out_xyzz + 32 * pa);
+  U.store(out_xyzz + 32 * pb);
+}
+
+// out_xyzz[i] = k * in_aff[i] for the one record at rec
+__global__ void __launch_bounds__(64) k_g1ntt_scale(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
+                                                    const uint32_t* __restrict__ rec, uint64_t n) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  g1ntt_mul<true>(g1_aff::load(in_aff + 16 * i), rec).store(out_xyzz + 32 * i);
+}
+
+// coordinates x * 2^261 (a table row, k_tab_to29) -> x * 2^256, out of place
+__global__ void __launch_bounds__(256) k_g1ntt_from29(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
+                                                      uint64_t nelem, G1NttWords c251) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nelem) return;
+  fq c;
+#pragma unroll
+  for (int k = 0; k < 8; k++) c.v[k] = c251.w[k];
+  (fq::load(in + 8 * i) * c).store(out + 8 * i);
+}
+
+G1NttSizes g1_ntt_sizes(int logn) {
+  const uint64_t n = 1ull << logn;
+  G1NttSizes z;
+  z.xyzz = 128 * n;
+  z.aff = 64 * n;
+  z.scratch = 32 * n;
+  z.tw = 4 * (uint64_t)G1NTT_TW_WORDS * (n / 2 + 1);
+  return z;
+}
+
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts) {
+  G1NttWords c{};
+  c.w[7] = 1u << 27;  // 2^251: (x 2^261)(2^251) / 2^256 = x 2^256 in the Montgomery product
+  if (npts) hipLaunchKernelGGL(k_g1ntt_from29, dim3(nb(2 * npts)), dim3(256), 0, st, out_aff, in29, 2 * npts, c);
+}
+
+void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
+                     const uint32_t scale_std[8]) {
+  G1NttWords one{}, scale;
+  for (int j = 0; j < 8; j++) scale.w[j] = scale_std[j];
+  hipLaunchKernelGGL(k_g1ntt_twiddles, dim3(1), dim3(256), 0, st, w.tw, (uint64_t)0, one, scale);
+  hipLaunchKernelGGL(k_g1ntt_scale, dim3(nb(n, 64)), dim3(64), 0, st, w.xyzz, in_aff, w.tw, n);
+  launch_batch_affine(st, out_aff, w.xyzz, w.scratch, n);
+}
+
+void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,
+                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping) {
+  const uint64_t n = 1ull << logn, half = n / 2;
+  G1NttWords root, scale{};
+  for (int j = 0; j < 8; j++) root.w[j] = root_mont[j];
+  bool scaled = false;
+  if (scale_std) {
+    for (int j = 0; j < 8; j++) {
+      scale.w[j] = scale_std[j];
+      scaled |= scale_std[j] != (j == 0 ? 1u : 0u);
+    }
+  }
+  hipLaunchKernelGGL(k_g1ntt_twiddles, dim3(nb(half + 1)), dim3(256), 0, st, w.tw, half, root, scale);
+  const uint32_t* src = in_aff;
+  for (int logh = 0; logh < logn; logh++) {
+    const bool last = logh == logn - 1;
+    const bool uni = mapping == G1NTT_MAP_WAVE || (mapping == G1NTT_MAP_AUTO && logh > 0);
+    if (uni && logn - 1 - logh >= 6)
+      hipLaunchKernelGGL(k_g1ntt_stage<true>, dim3(nb(half, 64)), dim3(64), 0, st, w.xyzz, src, w.tw, half, logh, logn,
+                         logh == 0);
+    else
+      hipLaunchKernelGGL(k_g1ntt_stage<false>, dim3(nb(half, 64)), dim3(64), 0, st, w.xyzz, src, w.tw, half, logh, logn,
+                         logh == 0);
+    uint32_t* dst = last && !scaled ? out_aff : w.aff;
+    launch_batch_affine(st, dst, w.xyzz, w.scratch, n);
+    src = dst;
+  }
+  if (scaled) {
+    hipLaunchKernelGGL(k_g1ntt_scale, dim3(nb(n, 64)), dim3(64), 0, st, w.xyzz, src, w.tw + G1NTT_TW_WORDS * half, n);
+    launch_batch_affine(st, out_aff, w.xyzz, w.scratch, n);
+  } else if (logn == 0 && out_aff != in_aff) {
+    hipMemcpyAsync(out_aff, in_aff, 64, hipMemcpyDeviceToDevice, st);
+  }
+}
+
+}  // namespace kgs

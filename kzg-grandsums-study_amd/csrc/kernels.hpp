@@ -1,4 +1,4 @@
-// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip). All pointers are device
+// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip, g1ntt.hip). All pointers are device
 // pointers to 32 B Montgomery Fr elements (uint32_t[8]) or 64 B affine / 128 B XYZZ G1 points,
 // unless stated otherwise. Launches are asynchronous on `st`.
 #pragma once
@@ -212,5 +212,30 @@ void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uin
                     uint32_t* T_out);
 void launch_fixed_base(hipStream_t st, uint32_t* out_xyzz, const uint32_t* sc, uint64_t count, const uint32_t* tbl);
 void launch_batch_affine(hipStream_t st, uint32_t* out_aff, const uint32_t* in_xyzz, uint32_t* scratch, uint64_t npts);
+
+// g1ntt.hip
+// Radix-2 NTT over G1, natural order in and out, n = 2^logn affine LEM points (zeros =
+// identity): out_j = scale * sum_i root^(i j) P_i. root_mont: a primitive n-th root of unity (Montgomery
+// words; its inverse for the inverse transform); scale_std: a standard-form factor < r applied to every
+// output (nullptr or 1: none). in_aff is only read, unless out_aff aliases it, which is allowed.
+constexpr int G1NTT_TW_WORDS = 16;  // a twiddle's signed-digit record: the masks of its +1 and of its -1 digits
+// which lanes of a wave share a twiddle: AUTO takes the per-wave mapping in every stage that has at
+// least 64 butterfly groups and a twiddle other than 1; LANE / WAVE force one for A/B timing
+// (kgs_bench_g1_ntt; WAVE still needs the 64 groups)
+constexpr int G1NTT_MAP_AUTO = 0, G1NTT_MAP_LANE = 1, G1NTT_MAP_WAVE = 2;
+struct G1NttSizes {  // bytes of the work buffers
+  uint64_t xyzz, aff, scratch, tw;
+};
+G1NttSizes g1_ntt_sizes(int logn);
+struct G1NttWork {
+  uint32_t *xyzz = nullptr, *aff = nullptr, *scratch = nullptr, *tw = nullptr;
+};
+void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,
+                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping);
+// out_aff[i] = scale_std * in_aff[i], i < n: the transform's scaling pass on its own (w sized for n points)
+void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
+                     const uint32_t scale_std[8]);
+// npts affine points of a table row (coordinates x * 2^261, msm_points_row29) -> the 2^256 form, out of place
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts);
 
 }  // namespace kgs

@@ -4,7 +4,8 @@
 // Host: argument checks, the window, the call's own device buffers ("mp_*" in the context's pool, grown
 // on demand, sized by msm_points_sizes(n, c)), and the finish: one Horner pass over the W * c bit-sum
 // points the device returns, then the affine conversion. Nothing of the prover's state is touched: not
-// the SRS tables, not mw / mw2 / work_npts, not the pinned staging.
+// the SRS tables, not mw / mw2 / work_npts, not the pinned staging. msm_points_over_row is the part after
+// the bases' conversion; kgs_commit_evals (g1_ntt.cpp) runs it over the cached Lagrange row.
 #include <mutex>
 
 #include "context.hpp"
@@ -54,10 +55,12 @@ void check_args(const void* points, const void* scalars, uint64_t n, int window_
   if (n && (!points || !scalars)) throw KgsError(KGS_E_ARG, "kgs_msm_points: NULL argument");
 }
 
-// The MSM on the context's device; the caller holds the context's mutex and has set the device.
-// points / scalars: host pointers (device = false) or device pointers. Ends with the main stream drained.
-void msm_points_gpu(kgs_ctx& c, const void* points, const void* scalars, bool device, uint64_t n, int window_c,
-                    uint8_t out[64]) {
+}  // namespace
+
+// The bucket passes over a row in msm_points_run's form and the host finish (context.hpp): what
+// kgs_msm_points runs after converting its bases, and kgs_commit_evals over the cached Lagrange row.
+void kgsi::msm_points_over_row(kgs_ctx& c, const uint32_t* row29, const uint32_t* d_scalars_std, uint64_t n,
+                               int window_c, uint8_t out[64]) {
   const int cc = window_c ? window_c : choose_points_c(n);
   const int W = (255 + cc - 1) / cc;
   if (n * (uint64_t)W > (1ull << 31))
@@ -66,8 +69,6 @@ void msm_points_gpu(kgs_ctx& c, const void* points, const void* scalars, bool de
   DrainOnError drain(&c);
   const MsmPointsSizes z = msm_points_sizes(n, cc);
   MsmWork w;
-  uint32_t* row = c.buf("mp_row", 64 * n);
-  uint32_t* sc = device ? nullptr : c.buf("mp_scal", 32 * n);
   w.digit = (int32_t*)c.buf("mp_digit", z.digit);
   w.sorted = c.buf("mp_sorted", z.sorted);
   w.lo = (uint8_t*)c.buf("mp_lo", z.lo);
@@ -82,16 +83,28 @@ void msm_points_gpu(kgs_ctx& c, const void* points, const void* scalars, bool de
   w.raw29 = c.buf("mp_raw29", z.raw29);
   w.part = c.buf("mp_part", z.part);
   uint32_t* dT = c.buf("mp_T", z.T);
-  HC(hipMemcpyAsync(row, points, 64 * n, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.st));
-  if (!device) HC(hipMemcpyAsync(sc, scalars, 32 * n, hipMemcpyHostToDevice, c.st));
-  msm_points_row29(c.st, row, n);
-  msm_points_run(c.st, w, row, device ? (const uint32_t*)scalars : sc, n, cc, dT);
+  msm_points_run(c.st, w, row29, d_scalars_std, n, cc, dT);
   check_launch();
   std::vector<uint8_t> T(z.T);
   HC(hipMemcpyAsync(T.data(), dT, z.T, hipMemcpyDeviceToHost, c.st));
   HC(hipStreamSynchronize(c.st));
   // sum_j 2^(c j) sum_k 2^k T[j][k] = sum_m 2^m T[m], m = j * c + k
   combine_partials(T.data(), z.T, 1, W * cc, out);
+}
+
+namespace {
+
+// The MSM on the context's device; the caller holds the context's mutex and has set the device.
+// points / scalars: host pointers (device = false) or device pointers. Ends with the main stream drained.
+void msm_points_gpu(kgs_ctx& c, const void* points, const void* scalars, bool device, uint64_t n, int window_c,
+                    uint8_t out[64]) {
+  DrainOnError drain(&c);
+  uint32_t* row = c.buf("mp_row", 64 * n);
+  uint32_t* sc = device ? nullptr : c.buf("mp_scal", 32 * n);
+  HC(hipMemcpyAsync(row, points, 64 * n, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.st));
+  if (!device) HC(hipMemcpyAsync(sc, scalars, 32 * n, hipMemcpyHostToDevice, c.st));
+  msm_points_row29(c.st, row, n);
+  msm_points_over_row(c, row, device ? (const uint32_t*)scalars : sc, n, window_c, out);
 }
 
 int msm_points_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, bool device, uint64_t n, int window_c,

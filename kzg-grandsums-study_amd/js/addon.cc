@@ -301,6 +301,7 @@ struct Job {
                // 5 = the multiplicities of a lookup table (lookupMultiplicities)
                // 6 = a batch of proofs against one ptau (verifyBatch)
                // 7 = one proof of several arguments (proveMulti)
+               // 8 = the G1 transform (g1Ntt), 9 = a commitment from evaluations (commitEvals)
   int rc = 0;
   std::string err;
   // load
@@ -320,9 +321,11 @@ struct Job {
   std::chrono::steady_clock::time_point t_queue, t_exec0, t_exec1;
   // proveGroup: rank r's context, SRS slice r of W, one native thread per rank
   std::vector<kgs_ctx_t*> ranks;
-  // msmPoints: bases and standard-form scalars (copied: the call returns before the work runs)
+  // msmPoints: bases and standard-form scalars (copied: the call returns before the work runs);
+  // g1Ntt: the points in `bases`, transformed in place; commitEvals: the evaluations in `scal`
   std::vector<uint8_t> bases, scal;
   uint8_t msm_out[64];
+  int ntt_logm = 0, ntt_inverse = 0;
   // verifyBatch: the proofs' shapes and bytes (copied), the verdicts and the call's diagnostics
   std::vector<kgs_proof_ref_t> vb_refs;
   std::vector<std::vector<uint8_t>> vb_bytes;
@@ -505,6 +508,10 @@ static void job_execute(napi_env, void* data) {
     return;
   } else if (j->op == 4) {
     j->rc = kgs_msm_points(j->ctx, j->bases.data(), j->scal.data(), j->scal.size() / 32, 0, j->msm_out);
+  } else if (j->op == 8) {
+    j->rc = kgs_g1_ntt(j->ctx, j->bases.data(), j->bases.data(), j->ntt_logm, j->ntt_inverse);
+  } else if (j->op == 9) {
+    j->rc = kgs_commit_evals(j->ctx, j->scal.data(), j->ntt_logm, j->msm_out);
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -533,8 +540,10 @@ static void job_complete(napi_env env, napi_status, void* data) {
   } else if (j->op == 2 || j->op == 5) {
     napi_resolve_deferred(env, j->deferred, adopt_u8(env, j->out, j->out_len));
     j->out = nullptr;
-  } else if (j->op == 4) {
+  } else if (j->op == 4 || j->op == 9) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->msm_out, 64));
+  } else if (j->op == 8) {
+    napi_resolve_deferred(env, j->deferred, make_u8(env, j->bases.data(), j->bases.size()));
   } else if (j->op == 6) {
     napi_value o, v;
     napi_create_object(env, &o);
@@ -1048,6 +1057,57 @@ static napi_value MsmPoints(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_msm_points");
 }
 
+// 2^k elements of `size` bytes -> k, or -1
+static int log2_count(size_t bytes, size_t size) {
+  if (bytes == 0 || bytes % size) return -1;
+  const size_t n = bytes / size;
+  if (n & (n - 1)) return -1;
+  int k = 0;
+  while (((size_t)1 << k) < n) k++;
+  return k;
+}
+
+// g1Ntt(ctx, pointsLem, inverse) -> Promise<2^k x 64 B affine LEM> on the GPU of ctx (the curve shim's
+// G1.fft / G1.ifft): kgs_g1_ntt over a copy of the points; ctx's SRS is left alone.
+static napi_value G1Ntt(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 8;
+  j->ctx = get_ctx(env, argv[0]);
+  j->bases = bytes_of(env, argv[1]);
+  bool inv = false;
+  napi_get_value_bool(env, argv[2], &inv);
+  j->ntt_inverse = inv ? 1 : 0;
+  j->ntt_logm = log2_count(j->bases.size(), 64);
+  if (j->ntt_logm < 0) {
+    delete j;
+    napi_throw_error(env, nullptr, "g1Ntt: expected a power of two of 64 B affine LEM points");
+    return nullptr;
+  }
+  return queue(env, j, "kgs_g1_ntt");
+}
+
+// commitEvals(ctx, evalsStd) -> Promise<64 B affine LEM> over the SRS resident on ctx (kgs_commit_evals):
+// the commitment to the polynomial with these 2^k standard-form evaluations
+static napi_value CommitEvals(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 9;
+  j->ctx = get_ctx(env, argv[0]);
+  j->scal = bytes_of(env, argv[1]);
+  j->ntt_logm = log2_count(j->scal.size(), 32);
+  if (j->ntt_logm < 0) {
+    delete j;
+    napi_throw_error(env, nullptr, "commitEvals: expected a power of two of 32 B standard-form evaluations");
+    return nullptr;
+  }
+  return queue(env, j, "kgs_commit_evals");
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1081,6 +1141,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"groupCreateLocal", nullptr, GroupCreateLocal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetGroup", nullptr, CtxSetGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"msmPoints", nullptr, MsmPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"g1Ntt", nullptr, G1Ntt, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"commitEvals", nullptr, CommitEvals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

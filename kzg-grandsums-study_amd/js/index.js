@@ -13,6 +13,9 @@ module.exports = {
     // the table's multiplicities from the witness and the table, and the prover that computes them itself
     lookup_multiplicities: require("./src/lookup/lookup_multiplicities"),
     lookup_kzg_grandsum_prover_from_table: require("./src/lookup/lookup_multiplicities").lookup_kzg_grandsum_prover_from_table,
+    // commit_evals(pTauFilename, evals): the commitment to a column given as standard-form evaluations, over
+    // the Lagrange-basis SRS built on the GPU (kgs_commit_evals)
+    commit_evals: require("./src/backend").commitEvals,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

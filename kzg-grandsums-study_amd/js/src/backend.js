@@ -196,6 +196,23 @@ async function proveMulti(pTauFilename, nBits, args) {
     });
 }
 
+// The commitment to the polynomial with the 2^k standard-form evaluations `evals` (an Evaluations, a
+// Uint8Array or a BigBuffer), over the SRS of pTauFilename (kgs_commit_evals: the Lagrange bases are
+// built on the GPU on first use and cached on the device) -> Promise<64 B affine LEM>
+async function commitEvals(pTauFilename, evals) {
+    const key = path.resolve(pTauFilename);
+    const e = contiguous(evals && evals.eval !== undefined ? evals.eval : evals);
+    const n = e.byteLength / 32;
+    if (!Number.isInteger(n) || n < 1 || (n & (n - 1)) !== 0) {
+        throw new Error("commit_evals: the evaluations must be a power of two of 32-byte elements");
+    }
+    const nBits = Math.round(Math.log2(n));
+    return withContext(async slot => {
+        await ensureSrs(slot, key, nBits);
+        return load().commitEvals(slot.ctx, e);
+    });
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -248,4 +265,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };

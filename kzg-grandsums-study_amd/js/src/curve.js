@@ -7,13 +7,13 @@
 //           the input's buffer kind (Uint8Array, or BigBuffer for a BigBuffer)
 //   G1 {F, zero, one, zeroAffine, oneAffine, add, sub, neg, double, eq, isZero, timesFr,
 //       timesScalar, toAffine, toJacobian, isValid, toRprUncompressed, fromRprUncompressed,
-//       toRprLEM, fromRprLEM, toObject, fromObject, toString, multiExpAffine}
+//       toRprLEM, fromRprLEM, toObject, fromObject, toString, multiExpAffine, fft, ifft}
 //   G2 {F, one, oneAffine, toAffine, fromRprLEM, toRprLEM}, pairingEq, name, terminate.
 // Field elements are 32-byte little-endian Montgomery Uint8Arrays; G1 points are 96 B Jacobian
 // (x, y, z; z = 0 for the zero point) or 64 B affine (x, y; (0, 0) = zero), G2 points 192 B / 128 B
 // over Fq2 (c0, c1). Group arithmetic here is BigInt host plumbing (the verifier's handful of point
-// operations); G1.multiExpAffine runs on the GPU through the addon (kgs_msm_points over the given bases)
-// and curve.pairingEq through the native optimal-ate pairing (kgs_pairing_eq). The hot path itself
+// operations); G1.multiExpAffine runs on the GPU through the addon (kgs_msm_points over the given bases),
+// so do G1.fft / G1.ifft (kgs_g1_ntt), and curve.pairingEq through the native optimal-ate pairing (kgs_pairing_eq). The hot path itself
 // is libkgs's prover.
 const crypto = require("crypto");
 const { BigBuffer, contiguous } = require("./bigbuffer");
@@ -227,6 +227,35 @@ function buildG1(F1, Fr, addon) {
             return encJ(dec(await p));
         },
     };
+    // [ffjs] G1.fft / G1.ifft(buff, inType, outType, logger, loggerTxt): the transform over G1 with the
+    // root Fr.w[log2 n], natural order in and out, on the GPU through the addon (kgs_g1_ntt). inType /
+    // outType: "affine" (64 B per point, the default) or "jacobian" (96 B); logger / loggerTxt are
+    // accepted and ignored. A buffer that does not hold a power of two of points throws.
+    const transform = (inverse) => async (buff, inType, outType, logger, loggerTxt) => {
+        inType = inType || "affine";
+        outType = outType || "affine";
+        for (const t of [inType, outType]) if (t !== "affine" && t !== "jacobian") throw new Error(`Invalid type: ${t}`);
+        const sIn = inType === "jacobian" ? 3 * n8 : 2 * n8, sOut = outType === "jacobian" ? 3 * n8 : 2 * n8;
+        const src = contiguous(buff);
+        const n = Math.floor(src.byteLength / sIn);
+        if (n === 0 || n * sIn !== src.byteLength || (n & (n - 1)) !== 0) throw new Error("fft must be multiple of 2");
+        let lem = src;
+        if (inType === "jacobian") {
+            lem = new Uint8Array(2 * n8 * n);
+            for (let i = 0; i < n; i++) lem.set(encA(dec(src.subarray(sIn * i, sIn * (i + 1)))), 2 * n8 * i);
+        }
+        const a = addon();
+        const run = () => a.g1Ntt(shimContext(a), lem, inverse);
+        const p = shimBusy.then(run, run);
+        shimBusy = p.catch(() => {});
+        const res = await p;
+        if (outType === "affine") return res;
+        const out = new Uint8Array(sOut * n);
+        for (let i = 0; i < n; i++) out.set(encJ(dec(res.subarray(2 * n8 * i, 2 * n8 * (i + 1)))), sOut * i);
+        return out;
+    };
+    G1.fft = transform(false);
+    G1.ifft = transform(true);
     return G1;
 }
 
