@@ -1,6 +1,6 @@
 // Internal interface of the prover library (not part of the C-ABI): the context, the shared
 // device tables and the host-side building blocks of a proof. Shared by prover.cpp (building blocks,
-// single prover, C-ABI), prover_rounds.cpp (the protocol rounds of the single and the multi-argument
+// single prover, C-ABI), msm_commit.cpp (SRS tables and the commitment MSM), prover_rounds.cpp (the protocol rounds of the single and the multi-argument
 // prover), prover_multi.cpp (the multi prover's entry points) and prover_dist.cpp (the
 // distributed prover over a rank group).
 #pragma once
@@ -243,7 +243,6 @@ struct kgs_ctx {
   MsmWork mw2;
   int msm_lanes = 2;  // kgs_ctx_set_msm_lanes
   bool ref_quirks = true;  // kgs_ctx_set_reference_quirks (ref_quirks.cpp); default on
-  uint64_t msm_nseg_max = 0;
   // domain tables (M = 2^logM; shared) and this context's views of them
   std::shared_ptr<DomainTables> dom;
   int logM = -1;
@@ -428,6 +427,18 @@ uint32_t* ref_quirks_quotient(kgs_ctx& c, bool gs, bool sel, bool lookup, int nb
                               const uint32_t* dF, const uint32_t* dT, const uint32_t* dS, const uint32_t* dSF,
                               const uint32_t* dST, uint64_t& qlen, uint32_t*& fmut);
 
+// ------------------------------------------------------------------ SRS and commitment MSM (msm_commit.cpp)
+#define CTX_LOCK(c) std::lock_guard<std::mutex> ctx_lock_(c->mu)
+// The window rule of both MSMs: clamp(ceil(log2 n) - 4, c_min, c_max); the environment variable
+// env_name overrides it for A/B timing when its value lies in [c_min, env_max] (else it is ignored)
+int choose_window(uint64_t n, int c_min, int c_max, const char* env_name, int env_max);
+int choose_c(uint64_t npts);
+// w's buffers from the context's pool, named prefix + <buffer> + suffix, of the sizes z
+void msm_work_from_pool(kgs_ctx& c, MsmWork& w, const std::string& prefix, const std::string& suffix,
+                        const MsmSizes& z);
+void ensure_msm_work(kgs_ctx& c);
+void load_points(kgs_ctx& c, const uint8_t* lem, uint64_t npts, int power, int nbits_max, const std::string& file,
+                 int srank = 0, int sworld = 1);
 // MSM commitment: device Pippenger -> c bit-sum points T_k (this rank's partial, pinned host)
 struct Commit {
   uint8_t* h_T = nullptr;   // pinned, c x 128 B (this rank's partial)

@@ -19,6 +19,7 @@
 // which yields the usual 256-bit Montgomery form (< 2q, one conditional subtraction).
 #pragma once
 #include "field.hpp"
+#include "msm_sizes.hpp"
 
 // CIOS rows that take the 32-bit m of fq29::reduce_row32 (at most 8: row 8 keeps the 29-bit m; the
 // column bounds are re-derived by tests/test_field29.py); 0 builds the all-29-bit-m products for A/B
@@ -294,7 +295,7 @@ struct fq29 {
   __device__ __forceinline__ static fq29 from_fq(const fq& a) { return mul(unpack(a.v), from(f29::C266)); }
 };
 
-constexpr int RAW29_WORDS = 40;  // g1_acc29::store_raw / load_raw record
+// g1_acc29::store_raw / load_raw record: RAW29_WORDS words (msm_sizes.hpp, which sizes the buffers of them)
 
 // Bucket accumulator in XYZZ over fq29 (coordinates < 2^258.6, normalised); infinity is a flag.
 struct g1_acc29 {
@@ -416,6 +417,7 @@ struct g1_acc29 {
 
   // raw form: 4 x 9 limbs + infinity flag, padded to 40 words (16-byte stores)
   __device__ __forceinline__ void store_raw(uint32_t* p) const {
+    static_assert(RAW29_WORDS == 40, "run record: 4 x 9 limbs, the infinity flag and 3 words of padding");
     uint32_t w[40];
 #pragma unroll
     for (int j = 0; j < 9; j++) {

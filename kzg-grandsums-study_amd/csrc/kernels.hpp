@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "field.hpp"
+#include "msm_sizes.hpp"
 
 namespace kgs {
 
@@ -49,17 +50,8 @@ struct MsmTables {
   bool zero_points = true;
 };
 
-constexpr int MSM_SL_G_MAX = 128;  // chunks per partition the lo-pass count buffer holds (msm.hip SL_G)
-// Bucket sort of an MSM with window c (msm.hip): LOB low bits of key - 1 are sorted inside a partition
-// (<= 8: the lo pass keeps them in a byte), the other c - 1 - LOB bits select one of NH = 2^(c-1-LOB)
-// partitions: 256 for 16 <= c <= 17, 512 / 1024 / 2048 for c = 18 / 19 / 20
-constexpr int MSM_NH_MAX = 2048;
-inline int msm_lob(int c) {
-  int lob = c - 1 < 7 ? c - 1 : 7;
-  if (c - 9 > lob) lob = c - 9 > 8 ? 8 : c - 9;
-  return lob;
-}
-inline int msm_nh(int c) { return (1 << (c - 1)) >> msm_lob(c); }
+// Work buffers of one MSM in flight, sized by msm_work_sizes (msm_sizes.hpp, with the bucket sort's
+// msm_lob / msm_nh and the kernels' constants)
 struct MsmWork {
   int32_t* digit = nullptr;  // reused as the partition-pass value array
   uint8_t* lo = nullptr;
@@ -67,7 +59,7 @@ struct MsmWork {
   uint32_t *counts = nullptr, *offsets = nullptr, *cursor = nullptr, *sorted = nullptr;
   uint32_t* part = nullptr;      // bucket row + column sums (2^h + 2^l run records, msm.hip k_rowcol)
   uint32_t* segowner = nullptr;  // bucket of each segment's first run
-  uint32_t* locnt = nullptr;     // lo pass: NH partitions x 256 lo x MSM_SL_G_MAX chunks counts / bases
+  uint32_t* locnt = nullptr;     // lo pass: NH partitions x 2^LOB lo x SL_G chunks counts / bases
   uint32_t* chunklist = nullptr; // combine levels: 3 lists of chunk-start segments
   uint32_t* chunkcnt = nullptr;  // their lengths
   uint32_t* raw29 = nullptr;     // accumulate output in the fq29 form (B + 1 + nseg entries x 160 B)
@@ -191,24 +183,28 @@ void msm_build_table(hipStream_t st, uint32_t* table, uint64_t npts, int c, int 
 // scalars[i] multiplies SRS point pbase + pstride * i (pbase + pstride * (N - 1) < tb.npts).
 // exclusive_acc: the bucket accumulation takes a SIMD's whole register file at its two waves (for a
 // context whose two MSM lanes would otherwise co-run their accumulations and delay each other's
-// tails); default: a 168-VGPR build that leaves room for other proofs' kernels (msm.hip).
-void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N, uint32_t* T_out,
+// tails); default: a 168-VGPR build that leaves room for other proofs' kernels (msm.hip). w sized by
+// msm_work_sizes(tb.npts, tb.c, tb.c, 2^(tb.c - 1), 1). Returns false, with nothing launched, for a window
+// the sort has no instantiation for (outside 7 .. 20).
+bool msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N, uint32_t* T_out,
              hipEvent_t* ev = nullptr, uint64_t pbase = 0, uint64_t pstride = 1, bool exclusive_acc = false);
 // Variable-base MSM over one row of points, no window tables (msm.hip). Window c in
 // MSM_POINTS_C_MIN .. MSM_POINTS_C_MAX: W = ceil(255 / c) windows of B = 2^(c-1) buckets each, and
 // W * B <= 2^19 is the largest key space the sort partitions (c = 16 reaches it exactly). The partition
 // pass stages 256 * 2 * W * 7 B + 12 B per partition in LDS: 133.0 KB at c = 7, of a workgroup's 160 KB.
 constexpr int MSM_POINTS_C_MIN = 7, MSM_POINTS_C_MAX = 16;
-struct MsmPointsSizes {  // bytes of the MsmWork buffers (same roles as in msm_run) and of the T output
-  uint64_t digit, sorted, lo, blockhist, counts, offsets, cursor, segowner, locnt, chunklist, raw29, part, T;
-};
-MsmPointsSizes msm_points_sizes(uint64_t N, int c);
+// bytes of the MsmWork buffers (same roles as in msm_run) and of the T output
+inline MsmSizes msm_points_work_sizes(uint64_t N, int c) {
+  const int W = msm_windows(c);
+  return msm_work_sizes(N, c, msm_points_c_sort(c), (uint64_t)W << (c - 1), W);
+}
 // row (N affine points, 256-bit Montgomery, zeros = identity) -> the accumulation's 29-bit form, in place
 void msm_points_row29(hipStream_t st, uint32_t* row, uint64_t N);
 // T_out[j * c + k] (XYZZ, 128 B) = sum of window j's buckets with bit k set, so that
 // sum_i s_i P_i = sum_m 2^m T_out[m] over m < W * c. scalars_std: N x 8 words, any 256-bit integers (taken
-// mod r). N >= 1, N * W <= 2^31; w sized by msm_points_sizes(N, c).
-void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
+// mod r). N >= 1, N * W <= 2^31; w sized by msm_points_work_sizes(N, c). Returns false, with nothing
+// launched, for a window outside MSM_POINTS_C_MIN .. MSM_POINTS_C_MAX.
+bool msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
                     uint32_t* T_out);
 void launch_fixed_base(hipStream_t st, uint32_t* out_xyzz, const uint32_t* sc, uint64_t count, const uint32_t* tbl);
 void launch_batch_affine(hipStream_t st, uint32_t* out_aff, const uint32_t* in_xyzz, uint32_t* scratch, uint64_t npts);

@@ -21,7 +21,6 @@
 namespace kgs {
 
 static inline unsigned nb(uint64_t work, unsigned bs = 256) { return (unsigned)((work + bs - 1) / bs); }
-constexpr int NH_MAX = MSM_NH_MAX;  // bucket-sort partitions (kernels.hpp msm_lob)
 
 // ------------------------------------------------------------------ window table precompute
 __global__ void __launch_bounds__(256) k_tab_dbl(uint32_t* __restrict__ tmp, const uint32_t* __restrict__ prev,
@@ -244,11 +243,6 @@ __device__ __forceinline__ uint32_t sort_key(int j, uint32_t m) {
   return VAR ? (uint32_t)j * (1u << (C - 1)) + m : m;
 }
 
-#ifndef KGS_SORT_SPT
-#define KGS_SORT_SPT 2
-#endif
-constexpr int SORT_SPT = KGS_SORT_SPT;  // scalars per thread in the histogram / partition passes
-
 // VAR: the scalars are standard forms of any 256-bit integer (reduced here and stored to std_out),
 // keys by sort_key; fixed base: std_out is unused
 template <int C, bool VAR = false>
@@ -330,7 +324,7 @@ __global__ void __launch_bounds__(256) k_sort_scan(uint32_t* __restrict__ hi_off
   }
 }
 
-// dynamic LDS (part_lds in msm_run): NS = 256 * SORT_SPT * W staged entries (4 B value, 2 B partition,
+// dynamic LDS (msm_part_lds): NS = 256 * SORT_SPT * W staged entries (4 B value, 2 B partition,
 // 1 B lo) and the block's per-partition base / offset / cursor (3 x NH words)
 // scalar i multiplies SRS point pbase + pstride * i (a contiguous or strided slice of the SRS).
 // VAR: keys by sort_key, and the entry's value is the point index i into the single row.
@@ -399,23 +393,14 @@ __global__ void __launch_bounds__(256) k_sort_part(uint32_t* __restrict__ tval, 
 // windows = 61 K entries = 4 chunks of 15.4 K), write amplification ~1 + 32 B / run. 4 chunks per
 // partition also make 1024 workgroups = exactly two rounds of 2 per CU at 2^20 (2048 = four at 2^21)
 // where 12 K-entry chunks made 1280 (two and a half rounds).
-// A/B knobs (-D): threads per k_lo_scatter block, entries per chunk (= LDS tile), max chunks per
-// partition
+// A/B knobs (-D): threads per k_lo_scatter block; entries per chunk (= LDS tile) and max chunks per
+// partition are SL_CHUNK and SL_G of msm_sizes.hpp, which also size the buffers
 #ifndef KGS_SL_THREADS
 #define KGS_SL_THREADS 1024
 #endif
-#ifndef KGS_SL_CHUNK
-#define KGS_SL_CHUNK 16384
-#endif
-#ifndef KGS_SL_G
-#define KGS_SL_G 64
-#endif
 constexpr int SL_THREADS = KGS_SL_THREADS;
-constexpr int SL_TILE = KGS_SL_CHUNK;
+constexpr int SL_TILE = SL_CHUNK;
 constexpr int SL_TILE_BIG = SL_TILE / 2;  // tiles of the multi-tile (skewed) path: 8 entries per thread
-constexpr int SL_G = KGS_SL_G;
-constexpr uint32_t SL_CHUNK = KGS_SL_CHUNK;
-static_assert(SL_G <= MSM_SL_G_MAX, "lo-pass count buffer (prover.cpp msm_locnt)");
 static_assert(SL_TILE % SL_THREADS == 0 && SL_TILE_BIG % SL_THREADS == 0, "lo-pass tile per thread");
 // waves per SIMD the k_lo_scatter build targets (its VGPR budget): a 1024-thread block is 4 waves per
 // SIMD, and at 8 it stays within 64 VGPRs
@@ -683,9 +668,7 @@ __global__ void __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu
 }
 
 // ------------------------------------------------------------------ bucket accumulation
-constexpr uint32_t CB_T = 16;  // partials per thread per combine level
-constexpr int CB_LEVELS = 3;
-
+// CB_T partials per thread per combine level, CB_LEVELS levels (msm_sizes.hpp)
 // Segment s (first run inside bucket [o0, o1)) starts a level chunk of `stride` partials x CB_T
 // when its bucket has more than CB_T partials and s is aligned: append it to that level's list.
 __device__ __forceinline__ void combine_enqueue(uint32_t* list, uint32_t* cnt, uint64_t s, uint64_t o0, uint64_t o1,
@@ -978,6 +961,9 @@ __global__ void __launch_bounds__(256) k_combine(uint32_t* __restrict__ raw, uin
 // T_{c-1} = S_B. Work: 2B adds for the row/column sums + c*2^(l-1) for the bit sums (c = 17: 0.13 M
 // adds instead of the (c-1)*B/2 = 0.52 M of summing every bucket once per set bit), at the minimal
 // depth of log2(B/2) + 1 dependent adds.
+// The tail kernels take the window j from blockIdx.y (gridDim.y: 1 for the fixed base, W for the variable
+// base): records behind raw + RAW29_WORDS * j * B, line sums behind rc + RAW29_WORDS * j * (2^h + 2^l),
+// the c points behind T + 32 * j * c. The offsets are uniform per workgroup (scalar arithmetic).
 // k_rowcol: block r < 2^h sums row r, block 2^h + r sums column r; one element per thread, LDS tree.
 __device__ __forceinline__ g1_acc29 block_tree_sum(g1_acc29 v, uint32_t* lds) {
   for (int stride = blockDim.x >> 1; stride > 0; stride >>= 1) {
@@ -994,7 +980,9 @@ __global__ void __launch_bounds__(256) k_rowcol(uint32_t* __restrict__ rc, const
   KGS_AUX_PRIO();
   __shared__ __attribute__((aligned(16))) uint32_t lds[128 * RAW29_WORDS];
   const int l = c / 2, h = c - 1 - l;  // l = ceil((c-1)/2)
-  const uint32_t r = blockIdx.x, t = threadIdx.x;
+  const uint32_t r = blockIdx.x, t = threadIdx.x, win = blockIdx.y;
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  rc += (uint64_t)RAW29_WORDS * win * ((1u << h) + (1u << l));
   const bool row = r < (1u << h);
   g1_acc29 v;
   v.set_inf();
@@ -1015,9 +1003,11 @@ constexpr uint32_t RC_LANES = 16;
 __global__ void __launch_bounds__(256) k_rowcol16(uint32_t* __restrict__ rc, const uint32_t* __restrict__ raw, int c) {
   KGS_AUX_PRIO();
   const int l = c / 2, h = c - 1 - l;
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, win = blockIdx.y;
   const uint32_t line = gid / RC_LANES, j = gid % RC_LANES;
   const uint32_t nlines = (1u << h) + (1u << l);
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  rc += (uint64_t)RAW29_WORDS * win * nlines;
   const bool row = line < (1u << h);
   const uint32_t n = row ? 1u << l : 1u << h;  // elements of this row / column (<= 256)
   g1_acc29 v;
@@ -1041,7 +1031,10 @@ __global__ void __launch_bounds__(128) k_bitsum_rc(uint32_t* __restrict__ T, con
   __shared__ __attribute__((aligned(16))) uint32_t lds[64 * RAW29_WORDS];
   const int l = c / 2, h = c - 1 - l;
   const int k = blockIdx.x;
-  const uint32_t t = threadIdx.x;
+  const uint32_t t = threadIdx.x, win = blockIdx.y;
+  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
+  rc += (uint64_t)RAW29_WORDS * win * ((1u << h) + (1u << l));
+  T += 32 * (uint64_t)win * c;
   g1_acc29 v;
   v.set_inf();
   if (k == c - 1) {
@@ -1059,22 +1052,68 @@ __global__ void __launch_bounds__(128) k_bitsum_rc(uint32_t* __restrict__ T, con
 }
 
 // ------------------------------------------------------------------ driver (device part)
+// w.cursor (msm_sizes.hpp): the partition offsets hi_off (NH + 1 words) and the exclusive scan cpre of
+// the lo pass's chunks per partition (NH + 1), NH_MAX + 8 words each, then the lo-pass block ->
+// partition table bpart
+struct SortCursors {
+  uint32_t *hi_off, *cpre, *bpart;
+  explicit SortCursors(const MsmWork& w)
+      : hi_off(w.cursor), cpre(w.cursor + NH_MAX + 8), bpart(w.cursor + 2 * (NH_MAX + 8)) {}
+};
+
+// The partition pass of both drivers: digit window c, sort window cs, B buckets. Fixed base: scalars are
+// Montgomery words and scalar i multiplies SRS point pbase + pstride * i of Nsrs. VAR: standard forms of
+// any 256-bit integers; the reduced forms (32 B each) go through w.sorted between the two passes: only
+// the lo pass writes it later, and it holds E = N * W >= 8 N words. Returns false, with nothing
+// launched, for a window without an instantiation: 7 .. 20 fixed base, 7 .. MSM_POINTS_C_MAX variable.
+template <bool VAR>
+static bool msm_sort(hipStream_t st, MsmWork& w, const uint32_t* scalars, uint64_t N, int c, int cs, uint32_t B,
+                     uint64_t Nsrs, uint64_t pbase, uint64_t pstride) {
+  const int lob = msm_lob(cs), NH = msm_nh(cs);  // msm_sizes.hpp
+  const uint32_t nblk = msm_sort_blocks(N);
+  const size_t part_lds = (size_t)msm_part_lds(msm_windows(c), NH);
+  const SortCursors cu(w);
+  uint32_t* ptot = w.counts;   // NH partition totals
+  uint32_t* bh = w.blockhist;  // NH x nblk
+  uint32_t* std_out = VAR ? w.sorted : nullptr;
+  const uint32_t* part_sc = VAR ? w.sorted : scalars;
+  switch (c) {
+#define KGS_SORT_C(CC)                                                                                          \
+  case CC:                                                                                                       \
+    if constexpr (!VAR || CC <= MSM_POINTS_C_MAX) {                                                              \
+      hipLaunchKernelGGL((k_sort_hist<CC, VAR>), dim3(nblk), dim3(256), 0, st, bh, scalars, N, lob, NH, nblk,    \
+                         std_out);                                                                               \
+      hipLaunchKernelGGL(k_sort_scan_blocks, dim3(NH), dim3(256), 0, st, bh, ptot, nblk);                        \
+      hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, st, cu.hi_off, ptot, NH, w.offsets, B, cu.cpre,     \
+                         cu.bpart);                                                                              \
+      hipLaunchKernelGGL((k_sort_part<CC, VAR>), dim3(nblk), dim3(256), part_lds, st, (uint32_t*)w.digit, w.lo,  \
+                         bh, ptot, cu.hi_off, part_sc, N, Nsrs, pbase, pstride, lob, NH, nblk);                  \
+      return true;                                                                                               \
+    }                                                                                                            \
+    return false;
+    KGS_SORT_C(7) KGS_SORT_C(8) KGS_SORT_C(9) KGS_SORT_C(10) KGS_SORT_C(11) KGS_SORT_C(12) KGS_SORT_C(13)
+    KGS_SORT_C(14) KGS_SORT_C(15) KGS_SORT_C(16) KGS_SORT_C(17) KGS_SORT_C(18) KGS_SORT_C(19) KGS_SORT_C(20)
+#undef KGS_SORT_C
+    default:
+      return false;
+  }
+}
+
 // The part of an MSM behind its partition pass, shared by the fixed-base driver (msm_run) and the
-// variable-base one (msm_points_run): the lo pass over NH partitions of 2^lob keys, the bucket
+// variable-base one (msm_points_run): the lo pass over the partitions of sort window cs, the bucket
 // accumulation of the E (upper bound) sorted entries against the points at `table`, and the bucket
 // totals, which replace records 1 .. B of w.raw29. zero_points: the points may include the zero point
 // (k_accumulate's ZP). ev: msm_run's events [1] .. [2].
-static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, bool zero_points, uint64_t E, int NH,
-                        int lob, uint32_t B, bool exclusive_acc, hipEvent_t* ev) {
-  uint32_t* hi_off = w.cursor;
-  uint32_t* cpre = w.cursor + NH_MAX + 8;
-  uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
+static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, bool zero_points, uint64_t E, int cs,
+                        uint32_t B, bool exclusive_acc, hipEvent_t* ev) {
+  const int lob = msm_lob(cs), NH = msm_nh(cs);
+  const SortCursors cu(w);
   // lo-pass grid: an upper bound of sum_p chunk_count(size_p) (blocks past cpre[NH] exit)
-  const uint64_t chunk_bound = std::min<uint64_t>((uint64_t)NH * SL_G, NH + E / SL_CHUNK);
-  hipLaunchKernelGGL(k_lo_count, dim3((unsigned)chunk_bound), dim3(LC_THREADS), 0, st, w.locnt, w.lo, hi_off, cpre,
-                     bpart, NH, lob);
+  const uint64_t chunk_bound = msm_chunk_bound(E, NH);
+  hipLaunchKernelGGL(k_lo_count, dim3((unsigned)chunk_bound), dim3(LC_THREADS), 0, st, w.locnt, w.lo, cu.hi_off,
+                     cu.cpre, cu.bpart, NH, lob);
   hipLaunchKernelGGL(k_lo_scatter, dim3((unsigned)chunk_bound), dim3(SL_THREADS), 0, st, w.sorted, w.offsets, w.locnt,
-                     (const uint32_t*)w.digit, w.lo, hi_off, cpre, bpart, NH, lob);
+                     (const uint32_t*)w.digit, w.lo, cu.hi_off, cu.cpre, cu.bpart, NH, lob);
   if (ev) hipEventRecord(ev[1], st);
   // one segment per resident thread (KGS_ACC_WAVES blocks of 256 per CU): every accumulate
   // thread runs once and they all finish together (a second, partial round of blocks would
@@ -1085,9 +1124,7 @@ static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, bool 
     return n;
   }();
   const uint64_t resident = (uint64_t)cus * KGS_ACC_WAVES * 256;
-  uint64_t L = (E + resident - 1) / resident;
-  if (L < 4) L = 4;
-  if ((E + L - 1) / L > (1ull << 18)) L = (E + (1ull << 18) - 1) >> 18;  // work buffers hold 2^18 + 2^16 segments
+  const uint64_t L = msm_seg_len(E, resident);  // at most MSM_SEG_MAX segments: what the work buffers hold
   const uint64_t nseg = (E + L - 1) / L;
   // chunk lists of the combine levels: list j holds <= nseg / CB_T^(j+1) + B entries
   uint32_t* cnt = w.chunkcnt;
@@ -1131,56 +1168,35 @@ static void msm_buckets(hipStream_t st, MsmWork& w, const uint32_t* table, bool 
                      (uint32_t)L, stride);
 }
 
-void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N,
+// The tail of both drivers: each window's row / column sums (2^h + 2^l lines: k_rowcol's block tree,
+// or k_rowcol16), then its c bit sums into T_out + 32 * window * c
+#ifndef KGS_ROWCOL16
+#define KGS_ROWCOL16 1
+#endif
+static void launch_tail(hipStream_t st, MsmWork& w, int c, int windows, bool block_tree, uint32_t* T_out) {
+  const uint32_t nlines = msm_tail_lines(c);
+  if (block_tree)
+    hipLaunchKernelGGL(k_rowcol, dim3(nlines, windows), dim3(256), 0, st, w.part, w.raw29, c);
+  else
+    hipLaunchKernelGGL(k_rowcol16, dim3((nlines * RC_LANES + 255) / 256, windows), dim3(256), 0, st, w.part, w.raw29,
+                       c);
+  hipLaunchKernelGGL(k_bitsum_rc, dim3(c, windows), dim3(128), 0, st, T_out, w.part, w.raw29, c);
+}
+
+bool msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* scalars, uint64_t N,
              uint32_t* T_out, hipEvent_t* ev, uint64_t pbase, uint64_t pstride, bool exclusive_acc) {
   // ev (optional, 5 events): [0] start, [1] after digits+sort, [2] after k_accumulate,
   // [3] after combine, [4] after bit-sum reduction
   if (ev) hipEventRecord(ev[0], st);
-  const int c = tb.c, W = tb.W;
+  const int c = tb.c;
   const uint32_t B = 1u << (c - 1);
-  // LOB bits of (key - 1) are sorted inside a partition (<= 8: tlo is a byte), the rest select one
-  // of NH = B >> LOB partitions (<= 256 up to c = 17, 2^(c-9) <= NH_MAX above)
-  const int lob = msm_lob(c);
-  const int NH = (int)(B >> lob);
-  const uint32_t nblk = (uint32_t)((N + 256 * SORT_SPT - 1) / (256 * SORT_SPT));
-  uint32_t* ptot = w.counts;                  // NH partition totals
-  uint32_t* hi_off = w.cursor;                // NH + 1
-  uint32_t* cpre = w.cursor + NH_MAX + 8;     // NH + 1: lo-pass chunks per partition, exclusive scan
-  uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);  // lo-pass block -> partition
-  uint32_t* bh = w.blockhist;                 // NH x nblk
-  const size_t part_lds = (size_t)256 * SORT_SPT * W * 7 + (size_t)12 * NH;
-  // both sort passes read the digits off the scalars' Montgomery words (scalar_digits)
-  switch (c) {
-#define KGS_SORT_C(CC)                                                                                         \
-  case CC:                                                                                                      \
-    hipLaunchKernelGGL(k_sort_hist<CC>, dim3(nblk), dim3(256), 0, st, bh, scalars, N, lob, NH, nblk,          \
-                       (uint32_t*)nullptr);                                                                     \
-    hipLaunchKernelGGL(k_sort_scan_blocks, dim3(NH), dim3(256), 0, st, bh, ptot, nblk);                       \
-    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, st, hi_off, ptot, NH, w.offsets, B, cpre, bpart); \
-    hipLaunchKernelGGL(k_sort_part<CC>, dim3(nblk), dim3(256), part_lds, st, (uint32_t*)w.digit, w.lo, bh,   \
-                       ptot, hi_off, scalars, N, tb.npts, pbase, pstride, lob, NH, nblk);                     \
-    break;
-    KGS_SORT_C(7) KGS_SORT_C(8) KGS_SORT_C(9) KGS_SORT_C(10) KGS_SORT_C(11) KGS_SORT_C(12)
-    KGS_SORT_C(13) KGS_SORT_C(14) KGS_SORT_C(15) KGS_SORT_C(16) KGS_SORT_C(17) KGS_SORT_C(18)
-    KGS_SORT_C(19) KGS_SORT_C(20)
-#undef KGS_SORT_C
-    default:
-      return;  // choose_c keeps 7 <= c <= KGS_C_MAX = 20
-  }
+  if (!msm_sort<false>(st, w, scalars, N, c, c, B, tb.npts, pbase, pstride)) return false;
   // E = N * W: upper bound of nonzero entries
-  msm_buckets(st, w, tb.table, tb.zero_points, N * (uint64_t)W, NH, lob, B, exclusive_acc, ev);
+  msm_buckets(st, w, tb.table, tb.zero_points, N * (uint64_t)tb.W, c, B, exclusive_acc, ev);
   if (ev) hipEventRecord(ev[3], st);
-  // row / column sums (2^h + 2^l blocks), then the c bit sums
-  const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
-#ifndef KGS_ROWCOL16
-#define KGS_ROWCOL16 1
-#endif
-  if (exclusive_acc || !KGS_ROWCOL16)
-    hipLaunchKernelGGL(k_rowcol, dim3(nlines), dim3(256), 0, st, w.part, w.raw29, c);
-  else
-    hipLaunchKernelGGL(k_rowcol16, dim3((nlines * RC_LANES + 255) / 256), dim3(256), 0, st, w.part, w.raw29, c);
-  hipLaunchKernelGGL(k_bitsum_rc, dim3(c), dim3(128), 0, st, T_out, w.part, w.raw29, c);
+  launch_tail(st, w, c, 1, exclusive_acc || !KGS_ROWCOL16, T_out);
   if (ev) hipEventRecord(ev[4], st);
+  return true;
 }
 
 // ------------------------------------------------------------------ variable-base MSM (kgs_msm_points)
@@ -1189,153 +1205,20 @@ void msm_run(hipStream_t st, const MsmTables& tb, MsmWork& w, const uint32_t* sc
 // bucket set of its own, records j * B + 1 .. j * B + B of raw29, and an entry's value is the point
 // index. Sort, accumulation and combine are the fixed-base kernels over W * B buckets (msm_buckets);
 // the tail below reduces each window's buckets to its c bit sums T_{j,k} = sum_{b has bit k} S_{j,b},
-// and the host finishes with sum_j 2^(c j) sum_k 2^k T_{j,k}: one Horner pass over the W * c points.
-//
-// The tail kernels are k_rowcol, k_rowcol16 and k_bitsum_rc with the window on blockIdx.y: window j
-// reads the records behind raw + RAW29_WORDS * j * B, writes its 2^h + 2^l line sums behind
-// rc + RAW29_WORDS * j * (2^h + 2^l) and its c points behind T + 32 * j * c.
-__global__ void __launch_bounds__(256) k_rowcol_win(uint32_t* __restrict__ rc, const uint32_t* __restrict__ raw, int c) {
-  KGS_AUX_PRIO();
-  __shared__ __attribute__((aligned(16))) uint32_t lds[128 * RAW29_WORDS];
-  const int l = c / 2, h = c - 1 - l;
-  const uint32_t r = blockIdx.x, t = threadIdx.x, win = blockIdx.y;
-  const uint32_t nlines = (1u << h) + (1u << l);
-  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
-  const bool row = r < (1u << h);
-  g1_acc29 v;
-  v.set_inf();
-  const uint32_t n = row ? 1u << l : 1u << h;  // elements of this row / column (<= 256 at c <= 16)
-  for (uint32_t e = t; e < n; e += 256) {
-    const uint32_t b = row ? (r << l) | e : (e << l) | (r - (1u << h));
-    if (b) v.add(g1_acc29::load_raw(run_rec(raw, b)));
-  }
-  v = block_tree_sum(v, lds);
-  if (t == 0) v.store_raw(rc + (uint64_t)RAW29_WORDS * (win * nlines + r));
-}
-
-__global__ void __launch_bounds__(256) k_rowcol16_win(uint32_t* __restrict__ rc, const uint32_t* __restrict__ raw,
-                                                      int c) {
-  KGS_AUX_PRIO();
-  const int l = c / 2, h = c - 1 - l;
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, win = blockIdx.y;
-  const uint32_t line = gid / RC_LANES, j = gid % RC_LANES;
-  const uint32_t nlines = (1u << h) + (1u << l);
-  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
-  const bool row = line < (1u << h);
-  const uint32_t n = row ? 1u << l : 1u << h;
-  g1_acc29 v;
-  v.set_inf();
-  if (line < nlines) {
-    for (uint32_t t = j; t < n; t += RC_LANES) {
-      const uint32_t b = row ? (line << l) | t : (t << l) | (line - (1u << h));
-      if (b) v.add(g1_acc29::load_raw(run_rec(raw, b)));
-    }
-  }
-#pragma unroll
-  for (int m = RC_LANES / 2; m >= 1; m >>= 1) v.add(shfl_xor_acc(v, m));  // every lane of the wave
-  if (line < nlines && j == 0) v.store_raw(rc + (uint64_t)RAW29_WORDS * (win * nlines + line));
-}
-
-__global__ void __launch_bounds__(128) k_bitsum_rc_win(uint32_t* __restrict__ T, const uint32_t* __restrict__ rc,
-                                                       const uint32_t* __restrict__ raw, int c) {
-  KGS_AUX_PRIO();
-  __shared__ __attribute__((aligned(16))) uint32_t lds[64 * RAW29_WORDS];
-  const int l = c / 2, h = c - 1 - l;
-  const int k = blockIdx.x;
-  const uint32_t t = threadIdx.x, win = blockIdx.y;
-  raw += (uint64_t)RAW29_WORDS * win * (1u << (c - 1));
-  rc += (uint64_t)RAW29_WORDS * win * ((1u << h) + (1u << l));
-  g1_acc29 v;
-  v.set_inf();
-  if (k == c - 1) {
-    if (t == 0) v = g1_acc29::load_raw(run_rec(raw, 1u << (c - 1)));
-  } else {
-    const int bits = k < l ? l : h, j = k < l ? k : k - l;
-    const uint32_t base = k < l ? 1u << h : 0u;
-    for (uint32_t e = t; e < (1u << (bits - 1)); e += 128) {
-      const uint32_t idx = ((e >> j) << (j + 1)) | (1u << j) | (e & ((1u << j) - 1));
-      v.add(g1_acc29::load_raw(rc + (uint64_t)RAW29_WORDS * (base + idx)));
-    }
-  }
-  v = block_tree_sum(v, lds);
-  if (t == 0) v.to_xyzz().store(T + 32 * ((uint64_t)win * c + k));
-}
-
-// window of the sort that holds the variable-base key space [1, W * B]: 2^(c_sort - 1) >= W * B
-static int points_c_sort(int c) {
-  const uint64_t keys = (uint64_t)((255 + c - 1) / c) << (c - 1);
-  int lg = 0;
-  while ((1ull << lg) < keys) lg++;
-  return lg + 1 < 7 ? 7 : lg + 1;
-}
-
-MsmPointsSizes msm_points_sizes(uint64_t N, int c) {
-  MsmPointsSizes z;
-  const uint64_t W = (255 + c - 1) / c, E = N * W, keys = W << (c - 1);
-  const int cs = points_c_sort(c);
-  const uint64_t NH = (uint64_t)msm_nh(cs), bsort = 1ull << (cs - 1);
-  const uint64_t nblk = (N + 256 * SORT_SPT - 1) / (256 * SORT_SPT);
-  uint64_t nseg = (1ull << 18) + 2;  // msm_buckets: L >= 4 and at most 2^18 segments
-  if (E / 4 + 2 < nseg) nseg = E / 4 + 2;
-  z.digit = 4 * E;
-  z.sorted = 4 * E;  // also the N reduced scalars between the two sort passes (W >= 16 > 8 words each)
-  z.lo = E + 16;
-  z.blockhist = 4 * NH * (nblk + 1);
-  z.counts = 4 * (NH + 8);
-  z.offsets = 4 * (bsort + 4);  // the lo pass writes the offsets of all 2^(c_sort - 1) keys
-  z.cursor = 4 * (2 * ((uint64_t)NH_MAX + 8) + NH + E / SL_CHUNK + 64);
-  z.segowner = 4 * nseg;
-  z.locnt = 4 * bsort * SL_G;  // (partition, lo, chunk) counts
-  z.chunklist = 4 * CB_LEVELS * (nseg / CB_T + keys + 16);
-  z.raw29 = 4 * (uint64_t)RAW29_WORDS * (keys + 2 + nseg);
-  z.part = 4 * (uint64_t)RAW29_WORDS * W * ((1ull << (c - 1 - c / 2)) + (1ull << (c / 2)));
-  z.T = 128 * W * (uint64_t)c;
-  return z;
-}
-
+// (launch_tail with gridDim.y = W), and the host finishes with sum_j 2^(c j) sum_k 2^k T_{j,k}: one
+// Horner pass over the W * c points.
 void msm_points_row29(hipStream_t st, uint32_t* row, uint64_t N) {
   if (N) hipLaunchKernelGGL(k_tab_to29, dim3(nb(2 * N)), dim3(256), 0, st, row, 2 * N);
 }
 
-void msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
+bool msm_points_run(hipStream_t st, MsmWork& w, const uint32_t* row29, const uint32_t* scalars_std, uint64_t N, int c,
                     uint32_t* T_out) {
-  const int W = (255 + c - 1) / c;
+  const int W = msm_windows(c), cs = msm_points_c_sort(c);
   const uint32_t B = (uint32_t)W << (c - 1);  // buckets of all windows
-  const int cs = points_c_sort(c);
-  const int lob = msm_lob(cs), NH = msm_nh(cs);
-  const uint32_t nblk = (uint32_t)((N + 256 * SORT_SPT - 1) / (256 * SORT_SPT));
-  uint32_t* ptot = w.counts;
-  uint32_t* hi_off = w.cursor;
-  uint32_t* cpre = w.cursor + NH_MAX + 8;
-  uint32_t* bpart = w.cursor + 2 * (NH_MAX + 8);
-  uint32_t* bh = w.blockhist;
-  const size_t part_lds = (size_t)256 * SORT_SPT * W * 7 + (size_t)12 * NH;
-  // the reduced scalars (32 B each) go through w.sorted between the two sort passes: only the lo pass
-  // writes it later, and it holds E = N * W >= 8 N words
-  uint32_t* scal_std = w.sorted;
-  switch (c) {
-#define KGS_SORT_C(CC)                                                                                               \
-  case CC:                                                                                                            \
-    hipLaunchKernelGGL((k_sort_hist<CC, true>), dim3(nblk), dim3(256), 0, st, bh, scalars_std, N, lob, NH, nblk,      \
-                       scal_std);                                                                                     \
-    hipLaunchKernelGGL(k_sort_scan_blocks, dim3(NH), dim3(256), 0, st, bh, ptot, nblk);                               \
-    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, st, hi_off, ptot, NH, w.offsets, B, cpre, bpart);          \
-    hipLaunchKernelGGL((k_sort_part<CC, true>), dim3(nblk), dim3(256), part_lds, st, (uint32_t*)w.digit, w.lo, bh,    \
-                       ptot, hi_off, scal_std, N, (uint64_t)0, (uint64_t)0, (uint64_t)0, lob, NH, nblk);              \
-    break;
-    KGS_SORT_C(7) KGS_SORT_C(8) KGS_SORT_C(9) KGS_SORT_C(10) KGS_SORT_C(11) KGS_SORT_C(12)
-    KGS_SORT_C(13) KGS_SORT_C(14) KGS_SORT_C(15) KGS_SORT_C(16)
-#undef KGS_SORT_C
-    default:
-      return;  // kgs_msm_points keeps MSM_POINTS_C_MIN <= c <= MSM_POINTS_C_MAX
-  }
-  msm_buckets(st, w, row29, true, N * (uint64_t)W, NH, lob, B, false, nullptr);
-  const uint32_t nlines = (1u << (c - 1 - c / 2)) + (1u << (c / 2));
-  if (!KGS_ROWCOL16)
-    hipLaunchKernelGGL(k_rowcol_win, dim3(nlines, W), dim3(256), 0, st, w.part, w.raw29, c);
-  else
-    hipLaunchKernelGGL(k_rowcol16_win, dim3((nlines * RC_LANES + 255) / 256, W), dim3(256), 0, st, w.part, w.raw29, c);
-  hipLaunchKernelGGL(k_bitsum_rc_win, dim3(c, W), dim3(128), 0, st, T_out, w.part, w.raw29, c);
+  if (!msm_sort<true>(st, w, scalars_std, N, c, cs, B, 0, 0, 0)) return false;
+  msm_buckets(st, w, row29, true, N * (uint64_t)W, cs, B, false, nullptr);
+  launch_tail(st, w, c, W, !KGS_ROWCOL16, T_out);
+  return true;
 }
 
 // ------------------------------------------------------------------ fixed-base (synthetic SRS)

@@ -2,7 +2,7 @@
 // DESIGN.md §17; kernels and the device driver in msm.hip, msm_points_run).
 //
 // Host: argument checks, the window, the call's own device buffers ("mp_*" in the context's pool, grown
-// on demand, sized by msm_points_sizes(n, c)), and the finish: one Horner pass over the W * c bit-sum
+// on demand, sized by msm_points_work_sizes(n, c)), and the finish: one Horner pass over the W * c bit-sum
 // points the device returns, then the affine conversion. Nothing of the prover's state is touched: not
 // the SRS tables, not mw / mw2 / work_npts, not the pinned staging. msm_points_over_row is the part after
 // the bases' conversion; kgs_commit_evals (g1_ntt.cpp) runs it over the cached Lagrange row.
@@ -34,16 +34,7 @@ static_assert(top_digits_fit(), "a window in MSM_POINTS_C_MIN .. MSM_POINTS_C_MA
 // clamp(ceil(log2 n) - 4, 7, 16): the fixed-base rule (choose_c), capped where the key space ends.
 // KGS_MSM_POINTS_C overrides it for A/B timing.
 int choose_points_c(uint64_t n) {
-  int lg = 0;
-  while ((1ull << lg) < n) lg++;
-  int c = lg - 4;
-  if (c < MSM_POINTS_C_MIN) c = MSM_POINTS_C_MIN;
-  if (c > MSM_POINTS_C_MAX) c = MSM_POINTS_C_MAX;
-  if (const char* e = getenv("KGS_MSM_POINTS_C")) {
-    const int v = atoi(e);
-    if (v >= MSM_POINTS_C_MIN && v <= MSM_POINTS_C_MAX) c = v;
-  }
-  return c;
+  return choose_window(n, MSM_POINTS_C_MIN, MSM_POINTS_C_MAX, "KGS_MSM_POINTS_C", MSM_POINTS_C_MAX);
 }
 
 void check_args(const void* points, const void* scalars, uint64_t n, int window_c, const uint8_t* out) {
@@ -67,23 +58,11 @@ void kgsi::msm_points_over_row(kgs_ctx& c, const uint32_t* row29, const uint32_t
     throw KgsError(KGS_E_ARG, "kgs_msm_points: window_c = " + std::to_string(cc) + " holds at most 2^31 / " +
                                   std::to_string(W) + " points");
   DrainOnError drain(&c);
-  const MsmPointsSizes z = msm_points_sizes(n, cc);
+  const MsmSizes z = msm_points_work_sizes(n, cc);
   MsmWork w;
-  w.digit = (int32_t*)c.buf("mp_digit", z.digit);
-  w.sorted = c.buf("mp_sorted", z.sorted);
-  w.lo = (uint8_t*)c.buf("mp_lo", z.lo);
-  w.blockhist = c.buf("mp_blockhist", z.blockhist);
-  w.counts = c.buf("mp_counts", z.counts);
-  w.offsets = c.buf("mp_offsets", z.offsets);
-  w.cursor = c.buf("mp_cursor", z.cursor);
-  w.segowner = c.buf("mp_segowner", z.segowner);
-  w.locnt = c.buf("mp_locnt", z.locnt);
-  w.chunklist = c.buf("mp_chunklist", z.chunklist);
-  w.chunkcnt = c.buf("mp_chunkcnt", 64);
-  w.raw29 = c.buf("mp_raw29", z.raw29);
-  w.part = c.buf("mp_part", z.part);
+  msm_work_from_pool(c, w, "mp_", "", z);
   uint32_t* dT = c.buf("mp_T", z.T);
-  msm_points_run(c.st, w, row29, d_scalars_std, n, cc, dT);
+  if (!msm_points_run(c.st, w, row29, d_scalars_std, n, cc, dT)) throw KgsError(KGS_E_ARG, "unsupported MSM window");
   check_launch();
   std::vector<uint8_t> T(z.T);
   HC(hipMemcpyAsync(T.data(), dT, z.T, hipMemcpyDeviceToHost, c.st));

@@ -159,6 +159,23 @@ def test_scaled_table_matches_msm_points(K, ref_ctx, files, monkeypatch, power, 
         assert len(seen) > 6  # the sets are not all the same point
 
 
+@pytest.mark.parametrize("power,c_env,c", LOADS[:2], ids=LOAD_IDS[:2])
+def test_two_lane_tail_matches_msm_points(K, ref_ctx, files, monkeypatch, power, c_env, c):
+    """a two-lane context reduces its buckets with the block-tree k_rowcol on a grid of one window
+    (gridDim.y = 1), msm_points with k_rowcol16 on a grid of W windows: the same tail kernels, and the
+    same bytes, for both parities of c (c = 7: l = 3, h = 3; c = 8: l = 4, h = 3)"""
+    paths, points = files
+    npts = (2 << power) - 1
+    rnd = random.Random(77 + c)
+    with loaded(K, paths[(power, c_env)], c_env, monkeypatch, c) as ctx:
+        ctx.set_msm_lanes(2)
+        k = rnd.randrange(1, R)
+        for what, s in (("random", [rnd.randrange(R) for _ in range(npts)]), ("all-equal", [k] * npts)):
+            want = ref_ctx.msm_points(points[power][:64 * npts], words([x * RHO % R for x in s]))
+            assert want != bytes(64)
+            assert ctx.msm(words(s)) == want, (what, c)
+
+
 # ------------------------------------------------------------------ degenerate SRS: the flagged kernel
 def neg_lem(p):
     y = int.from_bytes(p[32:], "little")
