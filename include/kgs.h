@@ -237,7 +237,10 @@ int kgs_host_register(void* ptr, uint64_t bytes);
 int kgs_host_unregister(void* ptr);
 /* Every kgs_prove / kgs_prove_device call returns with none of its transfers or kernels pending, on
  * its error paths too (a failed call drains the context's streams before it returns), so a caller may
- * unregister or free its buffers as soon as the call returns. kgs_ctx_idle reports 1 when no stream
+ * unregister or free its buffers as soon as the call returns. A context attached to a rank group
+ * (kgs_ctx_set_group) is exempt on its error paths: its main stream may wait in an exchange whose
+ * peers failed (the group's abort releases it), so a failed call does not drain it; such a context
+ * never reads or writes caller host memory in place. kgs_ctx_idle reports 1 when no stream
  * of the context has work outstanding, 0 otherwise (diagnostic; the tests check the contract). */
 int kgs_ctx_idle(kgs_ctx_t* ctx);
 /* Same with device-resident inputs (HIP device pointers on ctx's device). */

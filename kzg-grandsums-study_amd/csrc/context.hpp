@@ -1,7 +1,9 @@
 // Internal interface of the prover library (not part of the C-ABI): the context, the shared
 // device tables and the host-side building blocks of a proof. Shared by prover.cpp (building blocks,
-// single prover, C-ABI), msm_commit.cpp (SRS tables and the commitment MSM), prover_rounds.cpp (the protocol rounds of the single and the multi-argument
-// prover), prover_multi.cpp (the multi prover's entry points) and prover_dist.cpp (the
+// single prover, context entry points), host_boundary.cpp (kgs_prove over host buffers), primitives.cpp
+// (the C-ABI building blocks), srs_api.cpp (SRS / ptau entry points), msm_commit.cpp (SRS tables and the
+// commitment MSM), prover_rounds.cpp (the protocol rounds of the single and the multi-argument prover,
+// DESIGN.md §16), prover_multi.cpp (the multi prover's entry points) and prover_dist.cpp (the
 // distributed prover over a rank group).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,10 +17,12 @@
 #include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <array>
 #include <string>
 #include <vector>
 
 #include "../../include/kgs.h"
+#include "host_copy.hpp"
 #include "host_error.hpp"
 #include "host_field.hpp"
 #include "kernels.hpp"
@@ -267,14 +271,12 @@ struct kgs_ctx {
     // that fails is reported here, naming the stream: HIP errors are sticky, and unreported the fault
     // would surface at the next checked call of whatever runs next in the process (round 5's fault
     // surfaced that way in the NEXT test's first copy, profiles/r05/boundary/feed_per_piece_dma_fault.log)
-    const char* names[4] = {"main", "lane 2", "input copy", "write-back"};
-    const hipStream_t ss[4] = {st, st2, st_copy, st_wb};
-    for (int i = 0; i < 4; i++) {
-      if (!ss[i]) continue;
-      const hipError_t e = hipStreamSynchronize(ss[i]);
+    for (const auto& s : streams()) {
+      if (!s.st) continue;
+      const hipError_t e = hipStreamSynchronize(s.st);
       if (e != hipSuccess)
         fprintf(stderr, "kgs: context on device %d: its %s stream failed while draining at destruction: %s\n", device,
-                names[i], hipGetErrorString(e));
+                s.name, hipGetErrorString(e));
     }
     for (auto& kv : pool) hipFree(kv.second.p);
     if (h_pin) hipHostFree(h_pin);
@@ -295,6 +297,12 @@ struct kgs_ctx {
     }
   }
 
+  // every stream of the context, created or not yet (nullptr), with the name a report gives it
+  struct NamedStream { hipStream_t st; const char* name; };
+  std::array<NamedStream, 4> streams() const {
+    return {{{st, "main"}, {st2, "lane 2"}, {st_copy, "input copy"}, {st_wb, "write-back"}}};
+  }
+
   // A failed (re)allocation leaves the slot empty (bytes = 0), never a stale size over a freed block.
   uint32_t* buf(const std::string& name, size_t bytes) {
     DBuf& b = pool[name];
@@ -311,47 +319,33 @@ struct kgs_ctx {
     }
     return (uint32_t*)b.p;
   }
-  uint8_t* io_in(size_t bytes) {
-    if (h_in_bytes < bytes) {
-      if (h_in) {
-        sync();
-        HC(hipHostFree(h_in));
-        h_in = nullptr;
-        h_in_bytes = 0;
-      }
-      static const bool wc = [] {
-        const char* e = getenv("KGS_STAGE_WC");
-        return e && !strcmp(e, "1");
-      }();
-      HC(hipHostMalloc((void**)&h_in, bytes, wc ? hipHostMallocWriteCombined : hipHostMallocDefault));
-      h_in_bytes = bytes;
+  // a grow-only pinned host area: the old block is freed only after every stream is drained
+  void grow_pinned(uint8_t*& p, size_t& have, size_t bytes, unsigned flags = hipHostMallocDefault) {
+    if (have >= bytes) return;
+    if (p) {
+      sync();
+      HC(hipHostFree(p));
+      p = nullptr;
+      have = 0;
     }
+    HC(hipHostMalloc((void**)&p, bytes, flags));
+    have = bytes;
+  }
+  uint8_t* io_in(size_t bytes) {
+    static const bool wc = [] {
+      const char* e = getenv("KGS_STAGE_WC");
+      return e && !strcmp(e, "1");
+    }();
+    grow_pinned(h_in, h_in_bytes, bytes, wc ? hipHostMallocWriteCombined : hipHostMallocDefault);
     return h_in;
   }
   uint8_t* io(size_t bytes) {
-    if (h_io_bytes < bytes) {
-      if (h_io) {
-        sync();
-        HC(hipHostFree(h_io));
-        h_io = nullptr;
-        h_io_bytes = 0;
-      }
-      HC(hipHostMalloc((void**)&h_io, bytes, hipHostMallocDefault));
-      h_io_bytes = bytes;
-    }
+    grow_pinned(h_io, h_io_bytes, bytes);
     return h_io;
   }
   void ensure_pin(size_t bytes) {
-    if (h_pin_bytes >= bytes) return;
-    if (h_pin) {
-      sync();
-      HC(hipHostFree(h_pin));
-      h_pin = nullptr;
-      h_pin_bytes = 0;
-      h_pin_off = 0;
-    }
-    HC(hipHostMalloc((void**)&h_pin, bytes, hipHostMallocDefault));
-    h_pin_bytes = bytes;
+    if (h_pin_bytes < bytes) h_pin_off = 0;
+    grow_pinned(h_pin, h_pin_bytes, bytes);
   }
   // bump-allocated pinned region (valid until reset_staging(), i.e. until the next sync point)
   uint8_t* pin(size_t bytes) {
@@ -373,11 +367,9 @@ struct kgs_ctx {
     return d;
   }
   void sync() {
-    if (group) group->wait(st);  // the main stream carries the group's exchanges
-    else HC(hipStreamSynchronize(st));
-    if (st2) HC(hipStreamSynchronize(st2));
-    if (st_copy) HC(hipStreamSynchronize(st_copy));
-    if (st_wb) HC(hipStreamSynchronize(st_wb));
+    for (const auto& s : streams())
+      if (group && s.st == st) group->wait(st);  // the main stream carries the group's exchanges
+      else if (s.st) HC(hipStreamSynchronize(s.st));
   }
   void reset_staging() {
     sync();
@@ -681,8 +673,8 @@ struct DrainOnError {
   ~DrainOnError() {
     if (std::uncaught_exceptions() <= unwinding || ctx->group) return;
     hipSetDevice(ctx->device);
-    for (hipStream_t s : {ctx->st, ctx->st2, ctx->st_copy, ctx->st_wb})
-      if (s) (void)hipStreamSynchronize(s);
+    for (const auto& s : ctx->streams())
+      if (s.st) (void)hipStreamSynchronize(s.st);
     (void)hipGetLastError();
   }
 };
@@ -692,16 +684,5 @@ void prove_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out
 // the distributed prover (prover_dist.cpp): same inputs and outputs as prove_impl on every rank
 void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out);
 void prove_dist_group(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out);
-
-// host copies between pageable caller buffers and pinned staging, split over threads
-struct CopyJob {
-  uint8_t* dst;
-  const uint8_t* src;
-  size_t len;
-};
-void par_copy(const std::vector<CopyJob>& jobs);
-// one vector into pinned staging; ready(offset, len) on the calling thread per `dma`-byte span, in
-// order, once that span is copied (prover.cpp)
-void stream_copy(uint8_t* dst, const uint8_t* src, size_t len, size_t dma, const std::function<void(size_t, size_t)>& ready);
 
 }  // namespace kgsi

@@ -1,6 +1,6 @@
 // Error type and per-thread last-error message of the C-ABI (include/kgs.h: every entry point
 // returns a KGS_E_* code, kgs_last_error() the message of the calling thread's last failure).
-// Host-only; shared by the prover (prover.cpp) and the host-only units (ptau_io.cpp, verifier.cpp).
+// Host-only; shared by the prover (prover.cpp and the other C-ABI units) and the host-only units (ptau_io.cpp, verifier.cpp).
 #pragma once
 #include <stdexcept>
 #include <string>

@@ -687,7 +687,7 @@ void prove_dist_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* e
   launch_quotient_e(c.st, !gs, sel, Qe, cosS, cosF, cosT, cosSF, cosST, nxm1, d_qs, halo, Mc, W, r, (int)rot);
   check_launch();
   D.inv_e_to_cyc(Qc, Qe, lcs, true);
-  // Reference-quirks mode (ref_quirks.cpp; the single-GPU prover does the same in prover.cpp): where an
+  // Reference-quirks mode (ref_quirks.cpp; the single-GPU prover does the same in prover_rounds.cpp): where an
   // operand of degree 1 <= d < n/2 makes the reference's multiply compute something else (Q1), its
   // quotient chain is replayed on the gathered full operands, identically on every rank, and its Q —
   // or its error — replaces ours; otherwise only its RangeError on a zero quotient (Q3) differs.

@@ -69,7 +69,7 @@ def test_python_mirror_names():
 @pytest.mark.parametrize("length,span", [(1, 2 << 20), (1000, 2 << 20), (32 << 20, 2 << 20), ((32 << 20) + 77, 8 << 20),
                                          (3 << 20, 256 << 10), (5 << 20, 100)])
 def test_stream_copy_spans_in_order(lib, length, span):
-    """kgs_prove's staging copy (prover.cpp stream_copy, host only): every byte copied, every DMA span
+    """kgs_prove's staging copy (host_copy.cpp stream_copy, host only): every byte copied, every DMA span
     reported once, in address order, each only after all of its bytes were written."""
     import numpy as np
     rng = np.random.default_rng(length)

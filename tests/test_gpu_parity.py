@@ -723,6 +723,56 @@ def test_caller_pinned_inputs(K, which):
     ctx.close()
 
 
+def test_primitive_output_complete_on_return(K, ctx9):
+    """A primitive returns with its output complete: each wrapper that ends in the shared finish
+    (primitives.cpp) writes the same bytes into an output registered with kgs_host_register, which the
+    device-to-host copy reaches asynchronously, as into a pageable one, read the moment the call
+    returns. A contract test: kgs_fr_from_mont, kgs_ntt_ex (forward, natural order), kgs_lincomb (two
+    terms), kgs_poly_div_x_sub and kgs_quotient_ex (one unselected grand-sum argument on the 2n coset)
+    at n = 2^10."""
+    import ctypes
+    L, h = K.lib(), ctx9._h
+    nbits = 10
+    n = 1 << nbits
+    rnd = random.Random(20261020)
+    keep = []
+
+    def ptr(b):
+        p, k = K._ptr(b)
+        keep.append(k)
+        return p
+    a, b = (ptr(common.mont_bytes(rv(rnd, n))) for _ in range(2))
+    z = rnd.randrange(R)
+    c = rv(rnd, n)
+    c[0] = (c[0] - OP.Polynomial(c).evaluate(z)) % R  # (X - z) divides it
+    srcs, lens = (ctypes.c_void_p * 2)(a, b), (ctypes.c_uint64 * 2)(n, n - 3)
+    coefs, c0 = ptr(common.mont_bytes(rv(rnd, 2))), ptr(common.mont_bytes(rv(rnd, 1)))
+    pc, pz = ptr(common.mont_bytes(c)), ptr(bn.fr_to_bytes(z))
+    S, F, T = (ptr(common.mont_bytes(rv(rnd, 2 * n))) for _ in range(3))
+    arg = (K.QuotArg * 1)(K.QuotArg(K.GRANDSUM, S, F, T, None, None))
+    alpha, gamma = (ptr(common.mont_bytes(rv(rnd, 1))) for _ in range(2))
+    calls = {
+        "fr_from_mont": (32 * n, lambda out: L.kgs_fr_from_mont(h, a, out, n)),
+        "ntt_ex": (32 * n, lambda out: L.kgs_ntt_ex(h, a, n, out, nbits, 0)),
+        "lincomb": (32 * n, lambda out: L.kgs_lincomb(h, srcs, lens, coefs, 2, c0, n, out)),
+        "poly_div_x_sub": (32 * n, lambda out: L.kgs_poly_div_x_sub(h, pc, n, pz, out)),
+        "quotient_ex": (64 * n, lambda out: L.kgs_quotient_ex(h, nbits, nbits + 1, arg, 1, alpha, gamma, None, 0, out)),
+    }
+    for name, (size, call) in calls.items():
+        pageable = bytearray(size)
+        K._check(call(ptr(pageable)))
+        want = bytes(pageable)
+        assert any(want), name
+        registered = bytearray(size)
+        handle = K.host_register(registered)
+        try:
+            K._check(call(handle[0]))
+            got = bytes(registered)  # at once: nothing may still be in flight
+        finally:
+            K.host_unregister(handle)
+        assert got == want, name
+
+
 def test_failed_call_leaves_no_transfer_pending(K):
     """VERDICT r5 Next #1: a kgs_prove that fails after it has enqueued the DMAs of caller-pinned
     inputs (here: a domain larger than the loaded SRS, refused at the prover's start) returns with

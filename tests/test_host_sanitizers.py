@@ -8,6 +8,10 @@ them with malformed ptau files (truncated at every structural boundary, bad magi
 section sizes / n8 / curve / header size / power, missing sections) and malformed proofs (off-curve
 points, coordinates >= q, evaluations >= r, wrong statement), plus a seeded random fuzz loop.
 Every case must end with a clean exit and the expected verdict.
+
+The host copy engine (host_copy.cpp: par_copy, stream_copy and their thread pool, the only lock-free
+concurrent code of the library) is built with its stand-alone driver host_copy_check.cpp under
+ThreadSanitizer and under ASan + UBSan; each build runs with cached and with non-temporal stores.
 """
 import json
 import os
@@ -32,9 +36,10 @@ def exe():
     return EXE
 
 
-def run(exe, *args):
+def run(exe, *args, **extra_env):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87")
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=87",
+               TSAN_OPTIONS="halt_on_error=1:exitcode=88", **extra_env)
     p = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0, (args, p.returncode, p.stderr[-3000:])
     assert "Sanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-3000:]
@@ -182,3 +187,12 @@ def test_malformed_proofs(exe, tmp_path, idx):
 def test_fuzz(exe):
     out = run(exe, "fuzz", 20261016, 4000, common.oracle_ptau(3))
     assert "fuzz done iters 4000 accepted 0" in out
+
+
+@pytest.mark.parametrize("nt", ["0", "1"])
+@pytest.mark.parametrize("san", ["tsan", "asan"])
+def test_host_copy_engine(exe, san, nt):
+    """Four threads through stream_copy and par_copy at every length and offset that takes another
+    branch (host_copy_check.cpp), with KGS_COPY_NT=0 (memcpy) and =1 (the non-temporal store loop)."""
+    out = run(os.path.join(NATIVE, "build", "host_copy_check_" + san), KGS_COPY_NT=nt)
+    assert out.strip() == "host_copy_check ok (0 mismatches)"
