@@ -3,8 +3,11 @@
 // single prover, context entry points), host_boundary.cpp (kgs_prove over host buffers), primitives.cpp
 // (the C-ABI building blocks), srs_api.cpp (SRS / ptau entry points), msm_commit.cpp (SRS tables and the
 // commitment MSM), prover_rounds.cpp (the protocol rounds of the single and the multi-argument prover,
-// DESIGN.md §16), prover_multi.cpp (the multi prover's entry points) and prover_dist.cpp (the
-// distributed prover over a rank group).
+// DESIGN.md §16), prover_multi.cpp (the multi prover's entry points) and the distributed prover over a
+// rank group: prover_dist.cpp (its five rounds), dist_layout.hpp (the layouts, exchange steps
+// and exchange accounting), dist_math.hpp (its cross-rank host arithmetic) and dist_group.cpp (the
+// transports behind kgs_group, with rank_rendezvous.hpp, and the kgs_group_* entry points). The
+// Fiat-Shamir schedule of every prover and verifier is transcript.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -154,7 +157,7 @@ extern std::vector<std::weak_ptr<DomainTables>> g_dom_reg;
 
 using namespace kgsi;
 
-// Rank group of the distributed prover (transports in prover_dist.cpp). wait() drains a stream that
+// Rank group of the distributed prover (transports in dist_group.cpp). wait() drains a stream that
 // may hold the group's exchanges: a transport whose peers can hang (RCCL) polls it against a
 // deadline instead of blocking forever.
 struct kgs_group {
@@ -571,6 +574,7 @@ struct XiEvals {
   std::vector<Fr> fx, tx;
   Fr sFx = Fr::zero(), sTx = Fr::zero();
   Fr& at(R5Poly id, int idx) { return id == R5_F ? fx[idx] : id == R5_T ? tx[idx] : id == R5_SELF ? sFx : sTx; }
+  const Fr& at(R5Poly id, int idx) const { return const_cast<XiEvals*>(this)->at(id, idx); }
   const Fr* unpack(const ArgIn& a, const Fr* ev) {
     fx.assign(a.k, Fr::zero());
     tx.assign(a.k, Fr::zero());
@@ -615,9 +619,28 @@ struct R5 {
   Fr c0;
   std::vector<R5Term> terms;
 };
-R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma, const Fr& v,
-                const Fr& xi, const std::vector<Fr>& fx, const std::vector<Fr>& tx, const Fr& sFx, const Fr& sTx,
-                const Fr& sxiw, bool lookup, const Fr* fxi_override = nullptr);
+// one argument's linearisation r_j (prover.cpp): c0 and the coefficients of S, polT and Q
+R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma, const Fr& xi,
+                const std::vector<Fr>& fx, const std::vector<Fr>& tx, const Fr& sFx, const Fr& sTx, const Fr& sxiw,
+                bool lookup, const Fr* fxi_override = nullptr);
+// W_xi's numerator of m >= 1 arguments (prover.cpp), shared by the round engine (len = n) and the
+// distributed prover (len = its slice length, c0 kept on rank 0 only)
+struct OpenArg {
+  const ArgIn* in;
+  const ArgPolys* polys;
+  const XiEvals* x;
+  Fr sxiw;
+};
+LcTerms wxi_numerator(const std::vector<OpenArg>& args, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma,
+                      const std::vector<Fr>& dpow, const Fr& xi, const Fr& v, const uint32_t* Qc, uint64_t len,
+                      uint64_t qlen, const Fr* fxi_override = nullptr);
+// round 2's beta combinations of a vector argument (prover.cpp): the terms of fcomb, tcomb, polF, polT
+struct BetaComb {
+  LcTerms fcomb, tcomb, polF, polT;
+};
+BetaComb beta_combination(const std::vector<uint32_t*>& fm, const std::vector<uint32_t*>& tm,
+                          const std::vector<uint32_t*>& Fc, const std::vector<uint32_t*>& Tc, int k, const Fr& beta,
+                          uint64_t len);
 
 // What distinguishes the callers of prove_rounds. The engine never infers these from the argument count.
 struct RoundOpts {

@@ -334,12 +334,29 @@ void run_quotient(kgs_ctx& c, int nbits, int lcs, const std::vector<QuotIn>& arg
   }
 }
 
-// Round 5 (prover.js:320-413): r(X) + the opening numerator as sum_k coef_k P_k + c0, from the
-// challenges and round-4 evaluations. Z_H(xi), L1(xi) as polynomial_utils.js:1-19. Shared by the
-// single-GPU and the distributed prover.
-R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma, const Fr& v,
-                const Fr& xi, const std::vector<Fr>& fx, const std::vector<Fr>& tx, const Fr& sFx, const Fr& sTx,
-                const Fr& sxiw, bool lookup, const Fr* fxi_override) {
+// Round 2: the four beta combinations of a vector argument (k > 1), sum_i beta^i of the f_i and t_i on H
+// and of F_i and T_i in coefficient form, each over `len` elements. The callers launch them (run_lincomb)
+// on the streams they choose.
+BetaComb beta_combination(const std::vector<uint32_t*>& fm, const std::vector<uint32_t*>& tm,
+                          const std::vector<uint32_t*>& Fc, const std::vector<uint32_t*>& Tc, int k, const Fr& beta,
+                          uint64_t len) {
+  BetaComb b;
+  Fr bp = Fr::one();
+  for (int i = 0; i < k; i++) {
+    b.fcomb.add(fm[i], len, bp);
+    b.tcomb.add(tm[i], len, bp);
+    b.polF.add(Fc[i], len, bp);
+    b.polT.add(Tc[i], len, bp);
+    bp = bp * beta;
+  }
+  return b;
+}
+
+// Round 5 (prover.js:320-413): one argument's linearisation r(X) as sum_k coef_k P_k + c0 over S, polT and
+// Q, from the challenges and round-4 evaluations. Z_H(xi), L1(xi) as polynomial_utils.js:1-19.
+R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma, const Fr& xi,
+                const std::vector<Fr>& fx, const std::vector<Fr>& tx, const Fr& sFx, const Fr& sTx, const Fr& sxiw,
+                bool lookup, const Fr* fxi_override) {
   const uint64_t n = 1ull << nbits;
   Fr xn = xi;
   for (int i = 0; i < nbits; i++) xn = xn.sqr();
@@ -354,9 +371,6 @@ R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& 
   const Fr one = Fr::one();
   Fr selBin = Fr::zero();  // alpha^3 selTBin + alpha^2 selFBin (a lookup has no selTBin term)
   if (sel) selBin = ((lookup ? Fr::zero() : (sTx - sTx.sqr()) * alpha) + (sFx - sFx.sqr())) * alpha * alpha;
-  std::vector<Fr> vp(2 * k + 4);
-  vp[0] = one;
-  for (size_t i = 1; i < vp.size(); i++) vp[i] = vp[i - 1] * v;
   R5 r;
   Fr c0;
   if (gs) {
@@ -365,19 +379,6 @@ R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& 
     c0 = selBin + alpha * rc;
     r.terms.push_back({R5_S, 0, l1 - alpha * fg * tg});
     r.terms.push_back({R5_Q, 0, zh.neg()});
-    for (int i = 0; i < k; i++) {
-      r.terms.push_back({R5_F, i, vp[1 + i]});
-      c0 = c0 - vp[1 + i] * fx[i];
-    }
-    for (int i = 0; i < k; i++) {
-      r.terms.push_back({R5_T, i, vp[1 + k + i]});
-      c0 = c0 - vp[1 + k + i] * tx[i];
-    }
-    if (sel) {
-      r.terms.push_back({R5_SELF, 0, vp[2 * k + 1]});
-      r.terms.push_back({R5_SELT, 0, vp[2 * k + 2]});
-      c0 = c0 - vp[2 * k + 1] * sFx - vp[2 * k + 2] * sTx;
-    }
   } else {
     const Fr fg = fxi + gamma;
     const Fr dF = sel ? sFx * (fg - one) + one : fg;
@@ -385,18 +386,43 @@ R5 round5_terms(bool gs, bool sel, int k, int nbits, const Fr& alpha, const Fr& 
     r.terms.push_back({R5_POLT, 0, alpha * sxiw * (sel ? sTx : one)});
     r.terms.push_back({R5_S, 0, l1 - alpha * dF});
     r.terms.push_back({R5_Q, 0, zh.neg()});
-    for (int i = 0; i < k; i++) {
-      r.terms.push_back({R5_F, i, vp[1 + i]});
-      c0 = c0 - vp[1 + i] * fx[i];
-    }
-    if (sel) {
-      r.terms.push_back({R5_SELF, 0, vp[k + 1]});
-      r.terms.push_back({R5_SELT, 0, vp[k + 2]});
-      c0 = c0 - vp[k + 1] * sFx - vp[k + 2] * sTx;
-    }
   }
   r.c0 = c0;
   return r;
+}
+
+// W_xi's numerator (prover.js:320-413) of a proof of m >= 1 arguments, as the terms of one linear
+// combination: sum_j dpow[j] r_j - Z_H(xi) Q, then every polynomial opened at xi minus its value there,
+// one power of v each (ArgIn::each_xi by power). Round-1 polynomials, S and polT contribute `len`
+// elements, Q `qlen`; c0 is the constant term (global coefficient 0). fxi_override: the reference-quirks
+// replay's second value of polF (argument 0 only).
+LcTerms wxi_numerator(const std::vector<OpenArg>& args, int nbits, const Fr& alpha, const Fr& beta, const Fr& gamma,
+                      const std::vector<Fr>& dpow, const Fr& xi, const Fr& v, const uint32_t* Qc, uint64_t len,
+                      uint64_t qlen, const Fr* fxi_override) {
+  LcTerms lw;
+  Fr c0 = Fr::zero();
+  Fr zh_neg = Fr::zero();
+  for (size_t j = 0; j < args.size(); j++) {
+    const ArgIn& a = *args[j].in;
+    const XiEvals& x = *args[j].x;
+    const R5 r5 = round5_terms(a.gs(), a.sel(), a.k, nbits, alpha, beta, gamma, xi, x.fx, x.tx, x.sFx, x.sTx, args[j].sxiw,
+                               a.lk(), fxi_override);
+    for (const R5Term& t : r5.terms) {
+      if (t.id == R5_Q) zh_neg = t.coef;
+      else lw.add(args[j].polys->poly(t.id, t.idx), len, dpow[j] * t.coef);
+    }
+    c0 = c0 + dpow[j] * r5.c0;
+  }
+  lw.add(Qc, qlen, zh_neg);
+  Fr vp = Fr::one();
+  for (const OpenArg& o : args)
+    o.in->each_xi(true, [&](R5Poly id, int i) {
+      vp = vp * v;
+      lw.add(o.polys->poly(id, i), len, vp);
+      c0 = c0 - vp * o.x->at(id, i);
+    });
+  lw.c0 = c0;
+  return lw;
 }
 
 // The single-argument prover: its own checks, the rank-group dispatch, then the rounds (prover_rounds.cpp)

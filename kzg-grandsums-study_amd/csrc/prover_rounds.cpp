@@ -216,24 +216,20 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   HC(hipStreamSynchronize(c.st));
   if (c.st2) HC(hipStreamSynchronize(c.st2));
   if (hk.after_round1) hk.after_round1();
-  std::vector<std::vector<uint8_t>> com(ncom, std::vector<uint8_t>(64));
+  std::vector<uint8_t> com(64 * (size_t)ncom);  // proof order
   int ci = 0;
+  auto com_at = [&](int i) { return com.data() + 64 * (size_t)i; };
   {
     std::vector<uint8_t*> outs;
-    for (size_t i = 0; i < r1.size(); i++) outs.push_back(com[ci++].data());
+    for (size_t i = 0; i < r1.size(); i++) outs.push_back(com_at(ci++));
     commits_finish(c, r1, outs);
   }
   clock.lap(0);
 
   // ---------------- round 2: shared beta and gamma, every argument's S / Z (prover.js:181-231)
-  host::Transcript tr;
-  for (int i = 0; i < ci; i++) tr.add_commitment(com[i].data());
-  Fr beta = Fr::zero();
-  if (any_vec) {
-    beta = tr.challenge();
-    tr.add_scalar(beta);
-  }
-  const Fr gamma = tr.challenge();
+  host::Schedule sched;
+  const host::Schedule::BetaGamma bg = sched.after_round1(com_at(0), ci, any_vec);
+  const Fr &beta = bg.beta, &gamma = bg.gamma;
   // Two lanes (latency mode): the challenge-independent coset evaluations of F, T (+ selectors) run on
   // lane 1 from the start of the round, beside the builder's serial part (k_tile_inverse is one
   // workgroup) and S's inverse NTT on lane 0; S's commitment follows (S_j's on lane j & 1), S's coset
@@ -260,19 +256,11 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
       uint32_t* b_te = c.buf(name(j, "tcomb"), E);
       uint32_t* b_F = c.buf(name(j, "polF"), E);
       uint32_t* b_T = c.buf(name(j, "polT"), E);
-      LcTerms l1, l2, l3, l4;
-      Fr bp = Fr::one();
-      for (int i = 0; i < a.k; i++) {
-        l1.add(s.fm[i], n, bp);
-        l2.add(s.tm[i], n, bp);
-        l3.add(s.Fc[i], n, bp);
-        l4.add(s.Tc[i], n, bp);
-        bp = bp * beta;
-      }
-      run_lincomb(c.st, b_fe, n, l1);
-      run_lincomb(c.st, b_te, n, l2);
-      run_lincomb(s2, b_F, n, l3);
-      run_lincomb(s2, b_T, n, l4);
+      const BetaComb bc = beta_combination(s.fm, s.tm, s.Fc, s.Tc, a.k, beta, n);
+      run_lincomb(c.st, b_fe, n, bc.fcomb);
+      run_lincomb(c.st, b_te, n, bc.tcomb);
+      run_lincomb(s2, b_F, n, bc.polF);
+      run_lincomb(s2, b_T, n, bc.polT);
       s.fcomb = b_fe;
       s.tcomb = b_te;
       s.polF = b_F;
@@ -311,20 +299,14 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   const int iS = ci;
   {
     std::vector<uint8_t*> outs;
-    for (int j = 0; j < m; j++) outs.push_back(com[ci++].data());
+    for (int j = 0; j < m; j++) outs.push_back(com_at(ci++));
     commits_finish(c, r2, outs);
   }
   clock.lap(1);
 
   // ---------------- round 3: alpha, the separator delta, one quotient on a coset (prover.js:233-286)
-  tr.add_scalar(gamma);
-  for (int j = 0; j < m; j++) tr.add_commitment(com[iS + j].data());
-  const Fr alpha = tr.challenge();
-  Fr delta = Fr::one();
-  if (m > 1) {
-    tr.add_scalar(alpha);
-    delta = tr.challenge();
-  }
+  const host::Schedule::AlphaDelta ad = sched.after_round2(com_at(iS), m);
+  const Fr &alpha = ad.alpha, &delta = ad.delta;
   std::vector<Fr> dpow(m);
   dpow[0] = Fr::one();
   for (int j = 1; j < m; j++) dpow[j] = dpow[j - 1] * delta;
@@ -388,13 +370,11 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
     if (probe && ref_quotient_is_zero(probe)) throw KgsError(KGS_E_RANGE, "offset is out of bounds");
   }
   const int iQ = ci;
-  commit_finish(c, cQ, com[ci++].data());
+  commit_finish(c, cQ, com_at(ci++));
   clock.lap(2);
 
   // ---------------- round 4: evaluations at xi, argument by argument, then every S_j at xi w (prover.js:288-318)
-  tr.add_scalar(m > 1 ? delta : alpha);
-  tr.add_commitment(com[iQ].data());
-  const Fr xi = tr.challenge();
+  const Fr xi = sched.after_round3(com_at(iQ));
   const Fr xiw = xi * fr_w(nbits);
   // reference-quirks mode, polF's buffer shared and rewritten (Q2): the reference's later reads of polF
   // see the new values — polFs[0] itself for one multiset, only polF.evaluate (prover.js:360) for vectors
@@ -421,33 +401,10 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   clock.lap(3);
 
   // ---------------- round 5: r = sum_j delta^j r_j - Z_H(xi) Q, the two openings (prover.js:320-413)
-  tr.add_scalar(xi);
-  for (const Fr& e : evals) tr.add_scalar(e);
-  const Fr v = tr.challenge();
-  LcTerms lw;
-  Fr c0 = Fr::zero();
-  Fr zh_neg = Fr::zero();
-  for (int j = 0; j < m; j++) {
-    // round5_terms at v = 0 is argument j's linearisation alone: its opening terms get coefficient zero,
-    // c0 is r_j's constant and the S / polT coefficients are r_j's
-    const XiEvals& x = A[j].x;
-    const R5 r5 = round5_terms(args[j].gs(), args[j].sel(), args[j].k, nbits, alpha, beta, gamma, Fr::zero(), xi, x.fx, x.tx,
-                               x.sFx, x.sTx, A[j].sxiw, args[j].lk(), fxi_set ? &fxi_mut : nullptr);
-    for (const R5Term& t : r5.terms) {
-      if (t.id == R5_S || t.id == R5_POLT) lw.add(A[j].poly(t.id, t.idx), n, dpow[j] * t.coef);
-      else if (t.id == R5_Q) zh_neg = t.coef;
-    }
-    c0 = c0 + dpow[j] * r5.c0;
-  }
-  lw.add(Qc, qlen, zh_neg);
-  Fr vp = Fr::one();
-  for (int j = 0; j < m; j++)
-    args[j].each_xi(true, [&](R5Poly id, int i) {
-      vp = vp * v;
-      lw.add(A[j].poly(id, i), n, vp);
-      c0 = c0 - vp * A[j].x.at(id, i);
-    });
-  lw.c0 = c0;
+  const Fr v = sched.after_round4(evals.data(), evals.size());
+  std::vector<OpenArg> open;
+  for (int j = 0; j < m; j++) open.push_back({&args[j], &A[j], &A[j].x, A[j].sxiw});
+  const LcTerms lw = wxi_numerator(open, nbits, alpha, beta, gamma, dpow, xi, v, Qc, n, qlen, fxi_set ? &fxi_mut : nullptr);
   const uint64_t L = qlen > n ? qlen : n;
   uint32_t* Pbuf = c.buf("Pw", 32 * L);
   uint32_t* Wx = c.buf("Wxi", 32 * L);
@@ -463,7 +420,7 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
                 c.buf("div_carry", 32 * (dtiles + 1)));
   // W_{xi w} = sum_j v^j (S_j - S_j(xi w)) / (X - xi w)
   LcTerms l2;
-  vp = Fr::one();
+  Fr vp = Fr::one();
   for (int j = 0; j < m; j++) {
     l2.add(A[j].Sc, n, vp);
     l2.c0 = l2.c0 - vp * A[j].sxiw;
@@ -482,11 +439,11 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
   HC(hipMemcpyAsync(h_flags, flags, 4 * FL_WORDS, hipMemcpyDeviceToHost, c.st));
   c.sync();
   if (h_flags[FL_W] || h_flags[FL_W + 1]) throw KgsError(KGS_E_DOES_NOT_DIVIDE, "Polynomial does not divide");
-  commits_finish(c, {cW1, cW2}, {com[ci].data(), com[ci + 1].data()});
+  commits_finish(c, {cW1, cW2}, {com_at(ci), com_at(ci + 1)});
   ci += 2;
   clock.lap(4);
 
-  for (int i = 0; i < ncom; i++) memcpy(com_out + 64 * i, com[i].data(), 64);
+  memcpy(com_out, com.data(), com.size());
   for (size_t i = 0; i < evals.size(); i++) evals[i].to_bytes(ev_out + 32 * i);
   c.reset_staging();
 }

@@ -42,43 +42,9 @@ bool verify_impl(const Proof& p, int nbits, const host::G2A& tau_g2) {
     if (!lt_mod(p.ev + 32 * i, host::FR_MOD.p)) return false;
 
   // computeChallenges (grandsum verifier.js:246-312)
-  host::Transcript tr;
-  for (int i = 0; i < k; i++) {
-    tr.add_commitment(p.F(i));
-    tr.add_commitment(p.T(i));
-  }
-  if (p.sel) {
-    tr.add_commitment(p.selF());
-    tr.add_commitment(p.selT());
-  }
-  Fr beta = Fr::zero();
-  if (vec) {
-    beta = tr.challenge();
-    tr.add_scalar(beta);
-  }
-  const Fr gamma = tr.challenge();
-  tr.add_scalar(gamma);
-  tr.add_commitment(p.S());
-  const Fr alpha = tr.challenge();
-  tr.add_scalar(alpha);
-  tr.add_commitment(p.Q());
-  const Fr xi = tr.challenge();
-  tr.add_scalar(xi);
-  for (int i = 0; i < k; i++) {
-    tr.add_scalar(fr_at(p.fxi_raw(i)));
-    if (p.gs) tr.add_scalar(fr_at(p.txi_raw(i)));
-  }
-  if (p.sel) {
-    tr.add_scalar(fr_at(p.selFxi_raw()));
-    tr.add_scalar(fr_at(p.selTxi_raw()));
-  }
+  const host::Challenges ch = host::replay_schedule(p.com, p.base(), 1, p.ev, p.nev(), vec);
+  const Fr &beta = ch.beta, &gamma = ch.gamma, &alpha = ch.alpha, &xi = ch.xi, &v = ch.v, &u = ch.u;
   const Fr sxiw = fr_at(p.sxiw_raw());
-  tr.add_scalar(sxiw);
-  const Fr v = tr.challenge();
-  tr.add_scalar(v);
-  tr.add_commitment(p.Wxi());
-  tr.add_commitment(p.Wxiw());
-  const Fr u = tr.challenge();
 
   // Z_H(xi), L1(xi) (polynomial_utils.js:1-19)
   Fr xn = xi;

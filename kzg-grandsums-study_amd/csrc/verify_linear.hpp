@@ -100,6 +100,30 @@ inline const Fr& fr_w_cached(int k) {
   return tab[k];
 }
 
+// The challenges of a proof whose commitments lie in proof order (ncom1 round-1 commitments, m S, Q, Wxi,
+// Wxiw) and whose nev evaluations lie in transcript order: the schedule's stages back to back
+// (transcript.hpp; computeChallenges, grandsum verifier.js:246-312)
+struct Challenges {
+  Fr beta, gamma, alpha, delta, xi, v, u;
+};
+inline Challenges replay_schedule(const uint8_t* com, int ncom1, int m, const uint8_t* ev, int nev, bool any_vec) {
+  const uint8_t *S = com + 64 * (size_t)ncom1, *Q = S + 64 * (size_t)m;
+  std::vector<Fr> evals(nev);
+  for (int i = 0; i < nev; i++) evals[i] = Fr::from_bytes(ev + 32 * (size_t)i);
+  Schedule sch;
+  Challenges c;
+  const Schedule::BetaGamma bg = sch.after_round1(com, ncom1, any_vec);
+  const Schedule::AlphaDelta ad = sch.after_round2(S, m);
+  c.beta = bg.beta;
+  c.gamma = bg.gamma;
+  c.alpha = ad.alpha;
+  c.delta = ad.delta;
+  c.xi = sch.after_round3(Q);
+  c.v = sch.after_round4(evals.data(), evals.size());
+  c.u = sch.after_round5(Q + 64, Q + 128);
+  return c;
+}
+
 struct LinearForm {
   Fr a_wxi, a_wxiw;   // A = a_wxi * Wxi + a_wxiw * Wxiw
   std::vector<Fr> b;  // B = sum_j b[j] * C_j + b_g * G1, j in the commitment order of the proof
@@ -113,43 +137,9 @@ inline LinearForm linear_form(const Proof& p, int nbits) {
   const bool vec = k > 1;
   auto fr_at = [](const uint8_t* b) { return Fr::from_bytes(b); };
   // computeChallenges (grandsum verifier.js:246-312)
-  Transcript tr;
-  for (int i = 0; i < k; i++) {
-    tr.add_commitment(p.F(i));
-    tr.add_commitment(p.T(i));
-  }
-  if (p.sel) {
-    tr.add_commitment(p.selF());
-    tr.add_commitment(p.selT());
-  }
-  Fr beta = Fr::zero();
-  if (vec) {
-    beta = tr.challenge();
-    tr.add_scalar(beta);
-  }
-  const Fr gamma = tr.challenge();
-  tr.add_scalar(gamma);
-  tr.add_commitment(p.S());
-  const Fr alpha = tr.challenge();
-  tr.add_scalar(alpha);
-  tr.add_commitment(p.Q());
-  const Fr xi = tr.challenge();
-  tr.add_scalar(xi);
-  for (int i = 0; i < k; i++) {
-    tr.add_scalar(fr_at(p.fxi_raw(i)));
-    if (p.gs) tr.add_scalar(fr_at(p.txi_raw(i)));
-  }
-  if (p.sel) {
-    tr.add_scalar(fr_at(p.selFxi_raw()));
-    tr.add_scalar(fr_at(p.selTxi_raw()));
-  }
+  const Challenges ch = replay_schedule(p.com, p.base(), 1, p.ev, p.nev(), vec);
+  const Fr &beta = ch.beta, &gamma = ch.gamma, &alpha = ch.alpha, &xi = ch.xi, &v = ch.v, &u = ch.u;
   const Fr sxiw = fr_at(p.sxiw_raw());
-  tr.add_scalar(sxiw);
-  const Fr v = tr.challenge();
-  tr.add_scalar(v);
-  tr.add_commitment(p.Wxi());
-  tr.add_commitment(p.Wxiw());
-  const Fr u = tr.challenge();
 
   // Z_H(xi), L1(xi) (polynomial_utils.js:1-19)
   Fr xn = xi;
@@ -279,32 +269,8 @@ inline LinearForm linear_form_multi(const MultiProof& p, int nbits) {
   auto fr_at = [](const uint8_t* b) { return Fr::from_bytes(b); };
   bool any_vec = false;
   for (const ArgShape& a : p.args) any_vec |= a.npols > 1;
-  Transcript tr;
-  for (int i = 0; i < p.ncom1(); i++) tr.add_commitment(p.C(i));
-  Fr beta = Fr::zero();
-  if (any_vec) {
-    beta = tr.challenge();
-    tr.add_scalar(beta);
-  }
-  const Fr gamma = tr.challenge();
-  tr.add_scalar(gamma);
-  for (int j = 0; j < m; j++) tr.add_commitment(p.C(p.iS(j)));
-  const Fr alpha = tr.challenge();
-  tr.add_scalar(alpha);
-  Fr delta = Fr::one();
-  if (m > 1) {
-    delta = tr.challenge();
-    tr.add_scalar(delta);
-  }
-  tr.add_commitment(p.C(p.iQ()));
-  const Fr xi = tr.challenge();
-  tr.add_scalar(xi);
-  for (int i = 0; i < p.nev(); i++) tr.add_scalar(fr_at(p.E(i)));
-  const Fr v = tr.challenge();
-  tr.add_scalar(v);
-  tr.add_commitment(p.C(p.iWxi()));
-  tr.add_commitment(p.C(p.iWxiw()));
-  const Fr u = tr.challenge();
+  const Challenges ch = replay_schedule(p.com, p.ncom1(), m, p.ev, p.nev(), any_vec);
+  const Fr &beta = ch.beta, &gamma = ch.gamma, &alpha = ch.alpha, &delta = ch.delta, &xi = ch.xi, &v = ch.v, &u = ch.u;
 
   Fr xn = xi;
   for (int i = 0; i < nbits; i++) xn = xn.sqr();

@@ -149,7 +149,7 @@ def cyclic_to_block(cyc, W):
 def block_to_cyclic(blocks, W):
     """BLOCK -> CYCLIC (the openings before their commitment MSMs): rank r sends chunk d = its block's
     elements d + W t (global r M + d + W t, i.e. cyclic position r c2 + t of rank d); the received
-    chunks in source order ARE the cyclic slice (prover_dist.cpp block_to_cyc, dist.hip k_pack_b2c)"""
+    chunks in source order ARE the cyclic slice (dist_layout.hpp block_to_cyc, dist.hip k_pack_b2c)"""
     M = len(blocks[0])
     c2 = M // W
     send = [[blk[d + W * t] for d in range(W) for t in range(c2)] for blk in blocks]

@@ -12,6 +12,11 @@ Every case must end with a clean exit and the expected verdict.
 The host copy engine (host_copy.cpp: par_copy, stream_copy and their thread pool, the only lock-free
 concurrent code of the library) is built with its stand-alone driver host_copy_check.cpp under
 ThreadSanitizer and under ASan + UBSan; each build runs with cached and with non-temporal stores.
+
+The distributed prover's two HIP-free units have stand-alone drivers of the same kind: the in-process
+rank group's host rendezvous (rank_rendezvous.hpp: barrier, abort, time-out, host all-gather) under
+ThreadSanitizer and under ASan + UBSan, and its cross-rank host arithmetic (dist_math.hpp) under
+ASan + UBSan.
 """
 import json
 import os
@@ -196,3 +201,19 @@ def test_host_copy_engine(exe, san, nt):
     branch (host_copy_check.cpp), with KGS_COPY_NT=0 (memcpy) and =1 (the non-temporal store loop)."""
     out = run(os.path.join(NATIVE, "build", "host_copy_check_" + san), KGS_COPY_NT=nt)
     assert out.strip() == "host_copy_check ok (0 mismatches)"
+
+
+@pytest.mark.parametrize("san", ["tsan", "asan"])
+def test_rank_rendezvous(exe, san):
+    """Four rank threads through 2,000 all-gather rounds, an abort, a barrier time-out and a one-rank
+    group (rank_rendezvous_check.cpp)."""
+    out = run(os.path.join(NATIVE, "build", "rank_rendezvous_check_" + san))
+    assert out.strip() == "rank_rendezvous_check ok (0 mismatches)"
+
+
+@pytest.mark.parametrize("san", ["asan"])
+def test_dist_math(exe, san):
+    """Scan offsets, division carries, the Horner combine and the quotient halo pick at W = 1, 2, 4, 8
+    against their direct definitions (dist_math_check.cpp)."""
+    out = run(os.path.join(NATIVE, "build", "dist_math_check_" + san))
+    assert out.strip() == "dist_math_check ok (0 mismatches)"
