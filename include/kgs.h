@@ -603,6 +603,63 @@ int kgs_srs_lagrange(kgs_ctx_t* ctx, int nbits, uint8_t* out_lem);
 int kgs_commit_evals(kgs_ctx_t* ctx, const uint8_t* evals_std, int nbits, uint8_t out_lem[64]);
 /* Same with a device pointer (on ctx's device), read only. */
 int kgs_commit_evals_device(kgs_ctx_t* ctx, const void* d_evals_std, int nbits, uint8_t out_lem[64]);
+/* One scalar per point: out_lem[i] = s_i * P_i for i < n (the pointwise step of kgs_kzg_open_all as a
+ * primitive): per lane a signed-digit double-and-add, then one batched affine conversion.
+ *   points_lem   n affine LEM points as kgs_msm_points takes them: 64 zero bytes is the identity, points are
+ *                NOT validated (an unspecified result for a point off the curve, never a fault)
+ *   scalars_std  n x 32 B little-endian STANDARD form; any 256-bit integer, taken mod r
+ *   n            0 .. 2^26
+ *   out_lem      n canonical affine LEM points; an identity in or a scalar that is 0 mod r gives 64 zero
+ *                bytes. May alias points_lem.
+ * ctx == NULL computes on the host (no GPU is touched). Failures: KGS_E_ARG for an n above the limit, a NULL
+ * buffer with n > 0, a context attached to a rank group or with MSM sharding on. Context contract as for
+ * kgs_g1_ntt: own device buffers, no SRS, nothing of the prover's touched, idle on return. */
+int kgs_g1_mul_each(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t n, uint8_t* out_lem);
+/* Same with device pointers (on ctx's device; ctx must not be NULL). The inputs are only read, unless the
+ * output aliases the points, which is allowed. */
+int kgs_g1_mul_each_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t n,
+                           void* d_out_lem);
+/* One KZG opening over the resident SRS: y = p(z) and proof = [(p(X) - y) / (X - z)](tau) for the polynomial
+ * with the `len` coefficients coef_mont (32 B Montgomery each, as kgs_poly_eval takes them; len == 0: the
+ * zero polynomial), z any element of Fr. It composes what the rounds launch: the Horner tiles of
+ * kgs_poly_eval, the synthetic division of kgs_poly_div_x_sub (whose quotient does not depend on p's
+ * constant term) and kgs_msm over the len - 1 quotient coefficients; it adds no kernel. proof_lem: affine
+ * LEM, 64 zero bytes for a constant polynomial.
+ * Failures: KGS_E_SRS "no SRS loaded", or len - 1 above the resident points; KGS_E_ARG for a NULL argument, a
+ * context attached to a rank group or with MSM sharding on, an SRS loaded as a slice. The call holds the
+ * context's mutex and returns with nothing pending on its streams, on its error paths too. */
+int kgs_kzg_open(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, const uint8_t z_mont[32], uint8_t y_mont[32],
+                 uint8_t proof_lem[64]);
+/* All n = 2^nbits openings of one polynomial on its domain in O(n log n) group operations (Feist-Khovratovich;
+ * DESIGN.md §19): proofs_lem[i] is the proof kgs_kzg_open gives at z = Fr.w[nbits]^i, byte for byte. The
+ * quotient commitments are a Toeplitz product of the coefficients with the SRS, computed as one cyclic
+ * convolution of size 2n over G1: a forward Fr transform of the zero-padded coefficients, one scalar
+ * multiplication per point against the transform of the SRS side, an unscaled inverse G1 transform of size 2n
+ * and a forward one of size n. The SRS side is read off the resident window table's first row (as
+ * kgs_srs_lagrange does, no second read of the ptau file), transformed once per (SRS, nbits) and cached on
+ * the device under the rules of the Lagrange row: shared by the contexts of the device, published once
+ * complete, released with the SRS tables (128 B x 2^nbits).
+ *   coef_mont   len <= 2^nbits coefficients, 32 B Montgomery each (the rest are zero; len == 0 gives n
+ *               identities and zero evaluations)
+ *   nbits       0 .. min(23, the nbits_max the SRS was loaded for)
+ *   proofs_lem  2^nbits canonical affine LEM points, the identity as 64 zero bytes
+ *   evals_mont  NULL, or 2^nbits x 32 B that receive p(w^i): one more Fr transform of size n
+ * Failures: KGS_E_SRS "no SRS loaded"; KGS_E_ARG for an nbits out of range, len > 2^nbits, a NULL buffer with
+ * work to do, a context attached to a rank group or with MSM sharding on, an SRS loaded as a slice. Unlike
+ * kgs_g1_ntt this call, like kgs_ntt, may grow the device's shared domain tables (to 2^(nbits + 1)); the
+ * window tables, the Lagrange cache and the prover's MSM work buffers stay as they are. The call holds the
+ * context's mutex, uses device buffers of its own and returns with nothing pending on the context's
+ * streams, on its error paths too (kgs_ctx_idle). */
+int kgs_kzg_open_all(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, int nbits, uint8_t* proofs_lem,
+                     uint8_t* evals_mont);
+/* Same with device pointers (on ctx's device); d_coef_mont is only read. */
+int kgs_kzg_open_all_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, void* d_proofs_lem,
+                            void* d_evals_mont);
+/* Host only (no GPU, no context): the check of one opening, e(proof, [tau]_2) == e(C - y G + z proof, [1]_2).
+ * Returns 1 valid, 0 invalid (which includes a commitment or proof that is no canonical point of the curve
+ * and a z or y that is not below r), KGS_E_ARG for a NULL argument or a tau_g2 off its curve. */
+int kgs_kzg_verify(const uint8_t commit_lem[64], const uint8_t z_mont[32], const uint8_t y_mont[32],
+                   const uint8_t proof_lem[64], const uint8_t tau_g2[128]);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -623,6 +680,12 @@ int kgs_bench_ntt(kgs_ctx_t* ctx, void* d_buf, int logm, int reps, double* ms);
  * thread mapping, 1 one twiddle per lane, 2 one per wave wherever a stage has 64 groups. */
 int kgs_bench_g1_ntt(kgs_ctx_t* ctx, const void* d_in, void* d_out, int logm, int what, int mapping, int reps,
                      double* ms);
+/* `reps` runs of a leg of kgs_kzg_open_all_device for the 1 <= len <= 2^nbits device-resident coefficients,
+ * each between two events on ctx's stream, after one whole call (which builds and caches the SRS side):
+ * ms[r] = run r. what: 0 the call with the cache warm, 1 the build of the cached SRS side (not published),
+ * 2 the pointwise pass alone (2^(nbits + 1) per-lane multiplications and their affine conversion). */
+int kgs_bench_kzg_open_all(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int what, int reps,
+                           double* ms);
 /* The route kgs_commit_evals_device replaces, with the same device-resident input: to Montgomery form,
  * inverse NTT, kgs_msm over the resident window tables (profiles/g1_ntt_time.py times both by the wall
  * clock; each ends synchronised). */

@@ -176,6 +176,14 @@ def lib():
         L.kgs_srs_lagrange.argtypes = [ctypes.c_void_p, ctypes.c_int, c_u8p]
         L.kgs_commit_evals.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_int, c_u8p]
         L.kgs_commit_evals_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_u8p]
+        L.kgs_g1_mul_each.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64, c_u8p]
+        L.kgs_g1_mul_each_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                             ctypes.c_void_p]
+        L.kgs_kzg_open.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, c_u8p, c_u8p]
+        L.kgs_kzg_open_all.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_int, c_u8p, c_u8p]
+        L.kgs_kzg_open_all_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+        L.kgs_kzg_verify.argtypes = [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.kgs_ctx_set_reference_quirks.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -753,6 +761,53 @@ class Context:
         out = ctypes.create_string_buffer(64)
         _check(lib().kgs_commit_evals_device(self._h, d_evals, nbits, out))
         return out.raw
+
+    def g1_mul_each(self, points_lem, scalars_std):
+        """One scalar per point on the GPU (kgs_g1_mul_each): see the module-level g1_mul_each."""
+        return _g1_mul_each(self._h, points_lem, scalars_std)
+
+    def g1_mul_each_device(self, d_points, d_scalars, n, d_out):
+        """Device-resident twin (kgs_g1_mul_each_device): device pointers (ints) to n affine LEM points of
+        64 B, n standard-form scalars of 32 B and n x 64 writable bytes, which may be the points' own."""
+        _check(lib().kgs_g1_mul_each_device(self._h, d_points, d_scalars, n, d_out))
+
+    def kzg_open(self, coef_mont, z_mont):
+        """One KZG opening over the resident SRS (kgs_kzg_open): coef_mont holds the polynomial's Montgomery
+        coefficients (32 B each, any number the SRS covers), z_mont the point. Returns (y, proof):
+        y = p(z) as 32 B Montgomery and [(p(X) - y) / (X - z)](tau) as 64 B affine LEM."""
+        if len(coef_mont) % 32 or len(z_mont) != 32:
+            raise ValueError("coef_mont must hold 32-byte elements and z_mont one of them")
+        y, proof = ctypes.create_string_buffer(32), ctypes.create_string_buffer(64)
+        n = len(coef_mont) // 32
+        pc, kc = _ptr(coef_mont) if n else (None, None)  # read in place
+        _check(lib().kgs_kzg_open(self._h, pc, n, _buf(z_mont), y, proof))
+        del kc
+        return y.raw, proof.raw
+
+    def kzg_open_all(self, coef_mont, nbits=None, evals=False):
+        """All 2^nbits openings of a polynomial on its domain in O(n log n) (kgs_kzg_open_all, FK20): entry i
+        of the result is the proof kzg_open gives at Fr.w[nbits]^i, byte for byte. coef_mont: at most
+        2^nbits Montgomery coefficients of 32 B (nbits=None: the smallest domain that holds them). The SRS
+        side of the product is built on first use and cached on the device per (SRS, nbits). Returns
+        2^nbits x 64 B affine LEM, or with evals=True the pair (proofs, p(w^i) as 2^nbits x 32 B Montgomery)."""
+        n = len(coef_mont) // 32
+        if nbits is None:
+            nbits = max(n - 1, 0).bit_length()
+        if len(coef_mont) % 32:
+            raise ValueError("coef_mont must hold 32-byte elements")
+        m = 1 << nbits if 0 <= nbits <= 23 else 1  # else the library refuses before it writes
+        proofs = ctypes.create_string_buffer(64 * m)
+        ev = ctypes.create_string_buffer(32 * m) if evals else None
+        pc, kc = _ptr(coef_mont) if n else (None, None)  # read in place
+        _check(lib().kgs_kzg_open_all(self._h, pc, n, nbits, proofs, ev))
+        del kc
+        return (proofs.raw, ev.raw) if evals else proofs.raw
+
+    def kzg_open_all_device(self, d_coef, n, nbits, d_proofs, d_evals=None):
+        """Device-resident twin (kgs_kzg_open_all_device): d_coef is a device pointer (int) to n <= 2^nbits
+        Montgomery coefficients, read only; d_proofs to 2^nbits x 64 writable bytes; d_evals to 2^nbits x
+        32 writable bytes, or None."""
+        _check(lib().kgs_kzg_open_all_device(self._h, d_coef, n, nbits, d_proofs, d_evals))
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1336,6 +1391,52 @@ def commit_evals(pTauFilename, evals, device=0):
     ctx = _context(device)
     ctx.load_ptau(pTauFilename, nbits)
     return ctx.commit_evals(data, nbits)
+
+
+def _g1_mul_each(handle, points_lem, scalars_std):
+    if len(points_lem) % 64 or len(scalars_std) % 32 or len(points_lem) // 64 != len(scalars_std) // 32:
+        raise ValueError("points_lem / scalars_std must hold the same number of 64 B points / 32 B scalars")
+    n = len(points_lem) // 64
+    out = ctypes.create_string_buffer(max(64 * n, 1))
+    (pp, kp), (ps, ks) = _ptr(points_lem), _ptr(scalars_std)  # read in place
+    _check(lib().kgs_g1_mul_each(handle, pp if n else None, ps if n else None, n, out))
+    del kp, ks
+    return out.raw[:64 * n]
+
+
+def g1_mul_each(points_lem, scalars_std, device=0):
+    """out[i] = scalars[i] * points[i] (kgs_g1_mul_each): points 64 B affine LEM (the zero point allowed,
+    points are not validated), scalars 32 B little-endian standard form (any 256-bit integer, taken mod
+    r). Returns n x 64 B canonical affine LEM (zeros for the identity). device=None computes on the host."""
+    handle = None if device is None else _context(device).handle
+    return _g1_mul_each(handle, points_lem, scalars_std)
+
+
+def kzg_open_all(pTauFilename, coefs, device=0):
+    """All openings of the polynomial with the Montgomery coefficients `coefs` (a bytes-like of 32-byte
+    elements) on the smallest domain 2^nbits that holds them, over the SRS of pTauFilename
+    (kgs_kzg_open_all): returns (proofs, evals), 2^nbits x 64 B affine LEM and 2^nbits x 32 B Montgomery,
+    entry i for the point Fr.w[nbits]^i."""
+    if len(coefs) % 32:
+        raise ValueError("coefs must hold 32-byte elements")
+    nbits = max(len(coefs) // 32 - 1, 0).bit_length()
+    ctx = _context(device)
+    ctx.load_ptau(pTauFilename, nbits)
+    return ctx.kzg_open_all(coefs, nbits, evals=True)
+
+
+def kzg_verify(tau_g2, commit, z_mont, y_mont, proof):
+    """The check of one KZG opening on the host (kgs_kzg_verify): e(proof, [tau]_2) ==
+    e(commit - y G + z proof, [1]_2). tau_g2: 128 B LEM, or the name of a ptau file to read it from;
+    commit / proof 64 B affine LEM, z_mont / y_mont 32 B Montgomery. Returns a bool; a commitment or proof
+    that is no point of the curve is False."""
+    if len(commit) != 64 or len(proof) != 64 or len(z_mont) != 32 or len(y_mont) != 32:
+        raise ValueError("commit / proof hold 64 bytes, z_mont / y_mont 32")
+    if isinstance(tau_g2, (str, os.PathLike)) or len(tau_g2) != 128:
+        t2 = ctypes.create_string_buffer(128)
+        _check(lib().kgs_ptau_read_tau_g2(os.fsencode(tau_g2), t2))
+        tau_g2 = t2.raw
+    return _check(lib().kgs_kzg_verify(_buf(commit), _buf(z_mont), _buf(y_mont), _buf(proof), _buf(tau_g2))) == 1
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

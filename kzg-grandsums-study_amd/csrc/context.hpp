@@ -112,6 +112,21 @@ struct LagrangeRow {
   }
 };
 
+// The SRS side of kgs_kzg_open_all's Toeplitz product for n = 2^nbits (g1_ntt.cpp): the
+// forward G1 transform of size 2n of (s_{n-2}, .., s_0, identity ..) over table row 0, scaled by 1 / 2n;
+// 2n affine points in the 2^256 form, still carrying the row's rho
+struct FkRow {
+  int device = 0;
+  uint32_t* xhat = nullptr;
+  uint64_t n = 0;
+  ~FkRow() {
+    if (xhat) {
+      hipSetDevice(device);
+      hipFree(xhat);
+    }
+  }
+};
+
 struct SrsTables {
   int device = 0;
   std::string file;  // file identity (path + size + mtime) or "mem#<id>"
@@ -123,6 +138,7 @@ struct SrsTables {
   // nbits -> the Lagrange bases of the first 2^nbits points; read and published under g_reg_mu, built
   // outside it and published complete, released with the tables
   std::map<int, std::shared_ptr<LagrangeRow>> lagrange;
+  std::map<int, std::shared_ptr<FkRow>> fk;  // nbits -> kgs_kzg_open_all's row, under the same rules
   ~SrsTables() {
     if (tb.table) {
       hipSetDevice(device);

@@ -198,9 +198,236 @@ int commit_evals_entry(kgs_ctx_t* ctx, const void* evals, bool device, int nbits
   API_END
 }
 
+// ------------------------------------------------------------------ openings
+constexpr int KZG_OPEN_ALL_LOG_MAX = G1_NTT_LOG_MAX - 1;  // the Toeplitz product transforms 2n points
+constexpr uint64_t G1_MUL_EACH_MAX = 1ull << 26;
+
+// the refusals of the calls over the whole resident SRS, in kgs_srs_lagrange's words
+void check_open_all(const kgs_ctx& c, int nbits, const char* fn) {
+  check_ctx(c, fn);
+  if (nbits < 0 || nbits > KZG_OPEN_ALL_LOG_MAX)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": nbits must be in 0 .. " + std::to_string(KZG_OPEN_ALL_LOG_MAX));
+  check_lagrange(c, nbits, fn);
+}
+
+// The row of (the context's SRS, nbits), enqueued on the main stream and not yet published: the forward
+// transform of size 2n of x = (s_{n-2}, .., s_0, identity x (n + 1)) read off table row 0, scaled by 1 / 2n.
+// Row 0's rho = 2^-256 stays on the points: the pointwise pass multiplies by Montgomery words, which
+// carry 2^256.
+std::shared_ptr<FkRow> fk_build(kgs_ctx& c, int nbits) {
+  const uint64_t n = 1ull << nbits;
+  auto row = std::make_shared<FkRow>();
+  row->device = c.device;
+  row->n = n;
+  HC(dev_malloc((void**)&row->xhat, 128 * n));
+  uint32_t* x = c.buf("gn_io", 128 * n);
+  HC(hipMemsetAsync(x, 0, 128 * n, c.st));
+  launch_g1_from29(c.st, x, c.tb.table, n - 1, true);
+  const Fr scale = ninv_std(nbits + 1);
+  ntt_enqueue(c, row->xhat, x, nbits + 1, false, &scale);
+  return row;
+}
+
+// The cached row, built on first use under the Lagrange row's rules (lagrange_row)
+std::shared_ptr<FkRow> fk_row(kgs_ctx& c, int nbits) {
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    auto it = c.srs->fk.find(nbits);
+    if (it != c.srs->fk.end()) return it->second;
+  }
+  DrainOnError drain(&c);
+  const std::shared_ptr<FkRow> row = fk_build(c, nbits);
+  HC(hipStreamSynchronize(c.st));
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  auto& slot = c.srs->fk[nbits];
+  if (!slot) slot = row;  // else: built concurrently by another context and published first; ours is released
+  return slot;
+}
+
+// u = (the Fr transform's output words) x (the cached points), pointwise, affine, into w.aff
+void fk_pointwise(kgs_ctx& c, const G1NttWork& w, const FkRow& row, const uint32_t* chat_words) {
+  launch_g1_mul_each(c.st, w.xyzz, row.xhat, chat_words, 2 * row.n, false);
+  launch_batch_affine(c.st, w.aff, w.xyzz, w.scratch, 2 * row.n);
+}
+
+// All n = 2^nbits openings of the polynomial with the `len` <= n Montgomery coefficients at d_coef (device),
+// enqueued on the main stream (not synchronised): n affine LEM proofs into d_proofs, p(w^i) into d_evals
+// (or nullptr). The caller holds the context, has checked it (check_open_all) and reset its staging.
+void kzg_open_all_run(kgs_ctx& c, const uint32_t* d_coef, uint64_t len, int nbits, uint32_t* d_proofs,
+                      uint32_t* d_evals) {
+  const uint64_t n = 1ull << nbits;
+  const int logm = nbits + 1;
+  if (!len) {  // the zero polynomial
+    HC(hipMemsetAsync(d_proofs, 0, 64 * n, c.st));
+    if (d_evals) HC(hipMemsetAsync(d_evals, 0, 32 * n, c.st));
+    return;
+  }
+  const std::shared_ptr<FkRow> row = fk_row(c, nbits);
+  if (logm > c.logM) ensure_domain(c, logm);
+  uint32_t* sa = c.buf("fk_fr", 64 * n);
+  uint32_t* sb = c.buf("fk_chat", 64 * n);
+  uint32_t* h = c.buf("fk_h", 64 * n);
+  const G1NttWork w = ntt_work(c, logm);  // serves the transform of size n too
+  uint32_t root[8];
+  // c^ = the Fr transform of size 2n of the zero-padded coefficients, natural order
+  ntt_dif(c.st, sa, d_coef, len, logm, nullptr, c.tw_fwd, c.logM);
+  launch_bitrev_copy(c.st, sb, sa, logm);
+  fk_pointwise(c, w, *row, sb);
+  // u = the inverse transform without its 1 / 2n (the row has it), in place in w.aff; h_k = u_{n-1+k}
+  fr_words(ntt_root(logm, true), root);
+  g1_ntt_run(c.st, w, w.aff, w.aff, logm, root, nullptr, G1NTT_MAP_AUTO);
+  if (n > 1) HC(hipMemcpyAsync(h, w.aff + 16 * (n - 1), 64 * (n - 1), hipMemcpyDeviceToDevice, c.st));
+  HC(hipMemsetAsync(h + 16 * (n - 1), 0, 64, c.st));
+  fr_words(ntt_root(nbits, false), root);
+  g1_ntt_run(c.st, w, d_proofs, h, nbits, root, nullptr, G1NTT_MAP_AUTO);
+  if (d_evals) {
+    ntt_dif(c.st, sa, d_coef, len, nbits, nullptr, c.tw_fwd, c.logM);
+    launch_bitrev_copy(c.st, d_evals, sa, nbits);
+  }
+  check_launch();
+}
+
+int kzg_open_all_entry(kgs_ctx_t* ctx, const void* coef, uint64_t len, int nbits, void* proofs, void* evals,
+                       bool device) {
+  API_BEGIN
+  const char* fn = "kgs_kzg_open_all";
+  if (!ctx) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL ctx");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_open_all(*ctx, nbits, fn);
+  const uint64_t n = 1ull << nbits;
+  if (len > n)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": len = " + std::to_string(len) + " coefficients do not fit the domain of 2^" +
+                                  std::to_string(nbits) + " points.");
+  if (!proofs || (len && !coef)) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  if (device) {
+    kzg_open_all_run(c, (const uint32_t*)coef, len, nbits, (uint32_t*)proofs, (uint32_t*)evals);
+  } else {
+    uint32_t* dc = c.buf("fk_coef", 32 * (len ? len : 1));
+    uint32_t* dp = c.buf("fk_out", 64 * n);
+    uint32_t* de = evals ? c.buf("fk_ev", 32 * n) : nullptr;
+    if (len) HC(hipMemcpyAsync(dc, coef, 32 * len, hipMemcpyHostToDevice, c.st));
+    kzg_open_all_run(c, dc, len, nbits, dp, de);
+    HC(hipMemcpyAsync(proofs, dp, 64 * n, hipMemcpyDeviceToHost, c.st));
+    if (evals) HC(hipMemcpyAsync(evals, de, 32 * n, hipMemcpyDeviceToHost, c.st));
+  }
+  c.reset_staging();
+  API_END
+}
+
+int g1_mul_each_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, uint64_t n, void* out, bool device) {
+  API_BEGIN
+  const char* fn = "kgs_g1_mul_each";
+  if (n > G1_MUL_EACH_MAX) throw KgsError(KGS_E_ARG, std::string(fn) + ": at most 2^26 points");
+  if (n && (!points || !scalars || !out)) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (!ctx) {
+    if (device) throw KgsError(KGS_E_ARG, "kgs_g1_mul_each_device: NULL ctx");
+    for (uint64_t i = 0; i < n; i++)  // the group has order r: the integer multiple is the multiple mod r
+      host::g1_lincomb_segment((const uint8_t*)points + 64 * i, (const uint8_t*)scalars + 32 * i, 1)
+          .to_affine_lem((uint8_t*)out + 64 * i);
+    return KGS_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_ctx(*ctx, fn);
+  if (!n) return KGS_OK;
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  uint32_t* xyzz = c.buf("gn_xyzz", 128 * n);
+  uint32_t* scratch = c.buf("gn_scratch", 32 * n);
+  const uint32_t *dp = (const uint32_t*)points, *ds = (const uint32_t*)scalars;
+  uint32_t* dout = (uint32_t*)out;
+  if (!device) {
+    uint32_t* io = c.buf("gn_io", 64 * n);
+    uint32_t* sc = c.buf("fk_chat", 32 * n);
+    HC(hipMemcpyAsync(io, points, 64 * n, hipMemcpyHostToDevice, c.st));
+    HC(hipMemcpyAsync(sc, scalars, 32 * n, hipMemcpyHostToDevice, c.st));
+    dp = dout = io;
+    ds = sc;
+  }
+  launch_g1_mul_each(c.st, xyzz, dp, ds, n, true);
+  launch_batch_affine(c.st, dout, xyzz, scratch, n);
+  check_launch();
+  if (!device) HC(hipMemcpyAsync(out, dout, 64 * n, hipMemcpyDeviceToHost, c.st));
+  HC(hipStreamSynchronize(c.st));
+  API_END
+}
+
+// One opening over the resident SRS as the rounds compose it: the Horner tiles for y, the synthetic
+// division (whose quotient does not depend on the constant term, so p is divided as it is and the
+// remainder flag is not read), the fixed-base MSM of the quotient.
+void kzg_open_run(kgs_ctx& c, const uint8_t* coef_mont, uint64_t len, const Fr& z, uint8_t y_mont[32],
+                  uint8_t proof_lem[64]) {
+  c.reset_staging();
+  if (!len) {
+    memset(y_mont, 0, 32);
+    memset(proof_lem, 0, 64);
+    return;
+  }
+  uint32_t* a = c.buf("prim_a", 32 * len);
+  HC(hipMemcpyAsync(a, coef_mont, 32 * len, hipMemcpyHostToDevice, c.st));
+  EvalJob j = eval_launch(c, {a}, {len}, z, 0);
+  Commit cm;
+  if (len > 1) {
+    uint32_t* q = c.buf("prim_b", 32 * len);
+    const uint32_t dt = (uint32_t)((len + EVAL_TILE - 1) / EVAL_TILE);
+    uint32_t* flag = c.buf("flags", 64);
+    HC(hipMemsetAsync(flag, 0, 64, c.st));
+    launch_divide(c.st, q, flag, a, len, xpowers(c, z), c.buf("div_part", 32 * (dt + 1)),
+                  c.buf("div_carry", 32 * (dt + 1)));
+    check_launch();
+    cm = commit_launch(c, q, len - 1, 0);
+  }
+  c.sync();
+  eval_finish(j)[0].to_bytes(y_mont);
+  if (len > 1) commit_finish(c, cm, proof_lem);
+  else memset(proof_lem, 0, 64);
+  c.reset_staging();
+}
+
 }  // namespace
 
 extern "C" {
+
+int kgs_g1_mul_each(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t n, uint8_t* out_lem) {
+  return g1_mul_each_entry(ctx, points_lem, scalars_std, n, out_lem, false);
+}
+
+int kgs_g1_mul_each_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t n,
+                           void* d_out_lem) {
+  return g1_mul_each_entry(ctx, d_points_lem, d_scalars_std, n, d_out_lem, true);
+}
+
+int kgs_kzg_open(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, const uint8_t z_mont[32], uint8_t y_mont[32],
+                 uint8_t proof_lem[64]) {
+  API_BEGIN
+  const char* fn = "kgs_kzg_open";
+  if (!ctx) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL ctx");
+  if (!z_mont || !y_mont || !proof_lem || (len && !coef_mont)) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_ctx(*ctx, fn);
+  if (ctx->srs_power < 0 || !ctx->srs) throw KgsError(KGS_E_SRS, "no SRS loaded");
+  if (ctx->srs_slice_world > 1)
+    throw KgsError(KGS_E_ARG, std::string(fn) + " needs the whole SRS: this context holds a rank's slice of it.");
+  if (len > ctx->tb.npts + 1) throw KgsError(KGS_E_SRS, "MSM larger than the resident SRS");
+  HC(hipSetDevice(ctx->device));
+  DrainOnError drain(ctx);
+  kzg_open_run(*ctx, coef_mont, len, Fr::from_bytes(z_mont), y_mont, proof_lem);
+  API_END
+}
+
+int kgs_kzg_open_all(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, int nbits, uint8_t* proofs_lem,
+                     uint8_t* evals_mont) {
+  return kzg_open_all_entry(ctx, coef_mont, len, nbits, proofs_lem, evals_mont, false);
+}
+
+int kgs_kzg_open_all_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, void* d_proofs_lem,
+                            void* d_evals_mont) {
+  return kzg_open_all_entry(ctx, d_coef_mont, len, nbits, d_proofs_lem, d_evals_mont, true);
+}
 
 int kgs_g1_ntt(kgs_ctx_t* ctx, const uint8_t* points_lem, uint8_t* out_lem, int logm, int inverse) {
   return g1_ntt_entry(ctx, points_lem, out_lem, false, logm, inverse);
@@ -273,6 +500,53 @@ int kgs_bench_g1_ntt(kgs_ctx_t* ctx, const void* d_in, void* d_out, int logm, in
   }
   hipEventDestroy(e0);
   hipEventDestroy(e1);
+  API_END
+}
+
+// ---- timing helper of profiles/kzg_open_all_time.py
+int kgs_bench_kzg_open_all(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int what, int reps,
+                           double* ms) {
+  API_BEGIN
+  const char* fn = "kgs_bench_kzg_open_all";
+  if (!ctx || !d_coef_mont || !ms) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (what < 0 || what > 2 || reps < 1) throw KgsError(KGS_E_ARG, std::string(fn) + ": bad what / reps");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_open_all(*ctx, nbits, fn);
+  const uint64_t n = 1ull << nbits;
+  if (len < 1 || len > n) throw KgsError(KGS_E_ARG, std::string(fn) + ": len must be in 1 .. 2^nbits");
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  uint32_t* out = c.buf("fk_out", 64 * n);
+  // every leg after one whole call: the row cached, the buffers grown, c^ in "fk_chat"
+  kzg_open_all_run(c, (const uint32_t*)d_coef_mont, len, nbits, out, nullptr);
+  HC(hipStreamSynchronize(c.st));
+  const std::shared_ptr<FkRow> row = fk_row(c, nbits);
+  const G1NttWork w = ntt_work(c, nbits + 1);
+  const uint32_t* chat = c.buf("fk_chat", 64 * n);
+  hipEvent_t e0, e1;
+  HC(hipEventCreate(&e0));
+  HC(hipEventCreate(&e1));
+  for (int r = 0; r < reps; r++) {
+    std::shared_ptr<FkRow> built;
+    HC(hipEventRecord(e0, c.st));
+    if (what == 0)
+      kzg_open_all_run(c, (const uint32_t*)d_coef_mont, len, nbits, out, nullptr);
+    else if (what == 1)
+      built = fk_build(c, nbits);
+    else
+      fk_pointwise(c, w, *row, chat);
+    HC(hipEventRecord(e1, c.st));
+    check_launch();
+    HC(hipEventSynchronize(e1));
+    float f = 0;
+    HC(hipEventElapsedTime(&f, e0, e1));
+    ms[r] = f;
+  }
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  c.reset_staging();
   API_END
 }
 

@@ -150,16 +150,65 @@ __global__ void __launch_bounds__(64) k_g1ntt_scale(uint32_t* __restrict__ out_x
   g1ntt_mul<true>(g1_aff::load(in_aff + 16 * i), rec).store(out_xyzz + 32 * i);
 }
 
-// coordinates x * 2^261 (a table row, k_tab_to29) -> x * 2^256, out of place
+// out_xyzz[i] = k_i * in_aff[i], the scalar k_i = sc[8 i ..] another one in every lane (the pointwise
+// product of kgs_kzg_open_all, kgs_g1_mul_each). REDUCE: k_i is any 256-bit integer and is
+// taken mod r here (at most five subtractions); otherwise k_i < r as the Fr kernels leave it. The NAF
+// record is made in registers and shifted up one digit per doubling, so no digit is indexed at run
+// time and nothing goes to scratch or to a record buffer (130 VGPRs). The lanes of a wave share no digit:
+// the wave pays an addition wherever one of its lanes has one, which with 64 independent scalars is
+// nearly every one of the 254 positions, against ~85 for a shared record: 254 (9 + 10) field products
+// against 254 * 9 + 85 * 10, a factor 1.54 (measured 1.57 at 2^21 points). The record in
+// LDS instead (120 VGPRs, four waves per SIMD instead of three) measured the same time: the loop is bound
+// by the VALU, not by latency.
+template <bool REDUCE>
+__global__ void __launch_bounds__(64) k_g1_mul_each(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
+                                                    const uint32_t* __restrict__ sc, uint64_t n) {
+  KGS_AUX_PRIO();
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fr k = fr::load(sc + 8 * i);
+  if (REDUCE) {
+#pragma unroll 1
+    for (int t = 0; t < 5; t++) k = fr::reduce_once(k);  // 2^256 < 6 r
+  }
+  uint32_t rec[G1NTT_TW_WORDS];
+  naf_record(k.v, rec);
+  const g1_aff b = g1_aff::load(in_aff + 16 * i);
+  g1_xyzz r = g1_xyzz::inf();
+  if (!b.is_inf()) {
+#pragma unroll 1
+    for (int d = 0; d < 256; d++) {
+      r = r.dbl();
+      const uint32_t p = rec[7] >> 31, m = rec[15] >> 31;
+#pragma unroll
+      for (int w = 7; w > 0; w--) {
+        rec[w] = (rec[w] << 1) | (rec[w - 1] >> 31);
+        rec[8 + w] = (rec[8 + w] << 1) | (rec[8 + w - 1] >> 31);
+      }
+      rec[0] <<= 1;
+      rec[8] <<= 1;
+      if (p | m) {
+        g1_aff s = b;
+        if (m) s.y = s.y.neg();
+        r.add_aff(s);
+      }
+    }
+  }
+  r.store(out_xyzz + 32 * i);
+}
+
+// coordinates x * 2^261 (a table row, k_tab_to29) -> x * 2^256, out of place; nelem = 2 npts coordinates.
+// flip = npts - 1 writes the points in reverse order (0: in order)
 __global__ void __launch_bounds__(256) k_g1ntt_from29(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
-                                                      uint64_t nelem, G1NttWords c251) {
+                                                      uint64_t nelem, G1NttWords c251, uint64_t flip) {
   KGS_AUX_PRIO();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nelem) return;
   fq c;
 #pragma unroll
   for (int k = 0; k < 8; k++) c.v[k] = c251.w[k];
-  (fq::load(in + 8 * i) * c).store(out + 8 * i);
+  const uint64_t o = flip ? (((flip - (i >> 1)) << 1) | (i & 1)) : i;
+  (fq::load(in + 8 * i) * c).store(out + 8 * o);
 }
 
 G1NttSizes g1_ntt_sizes(int logn) {
@@ -172,10 +221,12 @@ G1NttSizes g1_ntt_sizes(int logn) {
   return z;
 }
 
-void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts) {
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed) {
   G1NttWords c{};
   c.w[7] = 1u << 27;  // 2^251: (x 2^261)(2^251) / 2^256 = x 2^256 in the Montgomery product
-  if (npts) hipLaunchKernelGGL(k_g1ntt_from29, dim3(nb(2 * npts)), dim3(256), 0, st, out_aff, in29, 2 * npts, c);
+  if (npts)
+    hipLaunchKernelGGL(k_g1ntt_from29, dim3(nb(2 * npts)), dim3(256), 0, st, out_aff, in29, 2 * npts, c,
+                       reversed ? npts - 1 : (uint64_t)0);
 }
 
 void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
@@ -185,6 +236,13 @@ void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, cons
   hipLaunchKernelGGL(k_g1ntt_twiddles, dim3(1), dim3(256), 0, st, w.tw, (uint64_t)0, one, scale);
   hipLaunchKernelGGL(k_g1ntt_scale, dim3(nb(n, 64)), dim3(64), 0, st, w.xyzz, in_aff, w.tw, n);
   launch_batch_affine(st, out_aff, w.xyzz, w.scratch, n);
+}
+
+void launch_g1_mul_each(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t n,
+                        bool reduce) {
+  if (!n) return;
+  auto* kern = reduce ? k_g1_mul_each<true> : k_g1_mul_each<false>;
+  hipLaunchKernelGGL(kern, dim3(nb(n, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, n);
 }
 
 void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,

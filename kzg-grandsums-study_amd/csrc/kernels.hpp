@@ -231,7 +231,13 @@ void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uin
 // out_aff[i] = scale_std * in_aff[i], i < n: the transform's scaling pass on its own (w sized for n points)
 void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
                      const uint32_t scale_std[8]);
-// npts affine points of a table row (coordinates x * 2^261, msm_points_row29) -> the 2^256 form, out of place
-void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts);
+// out_xyzz[i] = k_i * in_aff[i], i < n, a scalar of its own per point (follow with
+// launch_batch_affine). scalars: n x 8 words read as integers; reduce: any 256-bit integers, taken mod r,
+// else every k_i < r already (an Fr kernel's output words). in_aff: zeros = identity.
+void launch_g1_mul_each(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t n,
+                        bool reduce);
+// npts affine points of a table row (coordinates x * 2^261, msm_points_row29) -> the 2^256 form, out of
+// place; reversed: out_aff[npts - 1 - i] = point i
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed = false);
 
 }  // namespace kgs

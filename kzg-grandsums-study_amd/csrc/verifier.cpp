@@ -234,6 +234,26 @@ int kgs_pairing_eq(int npairs, const uint8_t* g1_lem, const uint8_t* g2_lem) {
   }
 }
 
+int kgs_kzg_verify(const uint8_t commit_lem[64], const uint8_t z_mont[32], const uint8_t y_mont[32],
+                   const uint8_t proof_lem[64], const uint8_t tau_g2[128]) {
+  if (!commit_lem || !z_mont || !y_mont || !proof_lem || !tau_g2) return KGS_E_ARG;
+  try {
+    const host::G2A t2 = host::g2_from_lem(tau_g2);
+    if (!host::g2_on_curve(t2)) return KGS_E_ARG;
+    if (!host::g1_valid(commit_lem) || !host::g1_valid(proof_lem) || !host::lt_mod(z_mont, host::FR_MOD.p) ||
+        !host::lt_mod(y_mont, host::FR_MOD.p))
+      return 0;
+    const G1 W = pt(proof_lem);
+    uint8_t g1gen[64];
+    host::g1_gen_lem(g1gen);
+    // e(-W, [tau]_2) e(C - y G + z W, [1]_2) == 1
+    const G1 B = pt(commit_lem).add(pt(g1gen).mul(Fr::from_bytes(y_mont)).neg()).add(W.mul(Fr::from_bytes(z_mont)));
+    return host::pairing_eq2(W.neg(), t2, B, host::g2_gen()) ? 1 : 0;
+  } catch (const std::exception&) {
+    return KGS_E_ARG;
+  }
+}
+
 int kgs_verify_ptau(int kind, const char* ptau_path, int nbits, int npols, int selected, const uint8_t* commitments,
                     const uint8_t* evaluations) {
   uint8_t t2[128];

@@ -302,6 +302,7 @@ struct Job {
                // 6 = a batch of proofs against one ptau (verifyBatch)
                // 7 = one proof of several arguments (proveMulti)
                // 8 = the G1 transform (g1Ntt), 9 = a commitment from evaluations (commitEvals)
+               // 10 = every opening of a polynomial on its domain (kzgOpenAll)
   int rc = 0;
   std::string err;
   // load
@@ -322,7 +323,8 @@ struct Job {
   // proveGroup: rank r's context, SRS slice r of W, one native thread per rank
   std::vector<kgs_ctx_t*> ranks;
   // msmPoints: bases and standard-form scalars (copied: the call returns before the work runs);
-  // g1Ntt: the points in `bases`, transformed in place; commitEvals: the evaluations in `scal`
+  // g1Ntt: the points in `bases`, transformed in place; commitEvals: the evaluations in `scal`;
+  // kzgOpenAll: the coefficients in `scal`, the proofs in `bases`, the evaluations in `ev`
   std::vector<uint8_t> bases, scal;
   uint8_t msm_out[64];
   int ntt_logm = 0, ntt_inverse = 0;
@@ -512,6 +514,10 @@ static void job_execute(napi_env, void* data) {
     j->rc = kgs_g1_ntt(j->ctx, j->bases.data(), j->bases.data(), j->ntt_logm, j->ntt_inverse);
   } else if (j->op == 9) {
     j->rc = kgs_commit_evals(j->ctx, j->scal.data(), j->ntt_logm, j->msm_out);
+  } else if (j->op == 10) {
+    j->bases.resize((size_t)64 << j->ntt_logm);
+    j->ev.resize((size_t)32 << j->ntt_logm);
+    j->rc = kgs_kzg_open_all(j->ctx, j->scal.data(), j->scal.size() / 32, j->ntt_logm, j->bases.data(), j->ev.data());
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -544,6 +550,12 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->msm_out, 64));
   } else if (j->op == 8) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->bases.data(), j->bases.size()));
+  } else if (j->op == 10) {
+    napi_value o;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "proofs", make_u8(env, j->bases.data(), j->bases.size()));
+    napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
+    napi_resolve_deferred(env, j->deferred, o);
   } else if (j->op == 6) {
     napi_value o, v;
     napi_create_object(env, &o);
@@ -1108,6 +1120,28 @@ static napi_value CommitEvals(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_commit_evals");
 }
 
+// kzgOpenAll(ctx, coefMont) -> Promise<{proofs, evals}> over the SRS resident on ctx (kgs_kzg_open_all): the
+// openings of the polynomial with these Montgomery coefficients at every point of the smallest domain
+// 2^k that holds them, 2^k x 64 B affine LEM, and its values there, 2^k x 32 B Montgomery
+static napi_value KzgOpenAll(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 10;
+  j->ctx = get_ctx(env, argv[0]);
+  j->scal = bytes_of(env, argv[1]);
+  const size_t n = j->scal.size() / 32;
+  if (j->scal.size() % 32 || n > ((size_t)1 << 23)) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgOpenAll: expected at most 2^23 Montgomery coefficients of 32 B");
+    return nullptr;
+  }
+  j->ntt_logm = 0;
+  while (((size_t)1 << j->ntt_logm) < n) j->ntt_logm++;
+  return queue(env, j, "kgs_kzg_open_all");
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1143,6 +1177,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"msmPoints", nullptr, MsmPoints, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"g1Ntt", nullptr, G1Ntt, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitEvals", nullptr, CommitEvals, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgOpenAll", nullptr, KzgOpenAll, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -16,6 +16,10 @@ module.exports = {
     // commit_evals(pTauFilename, evals): the commitment to a column given as standard-form evaluations, over
     // the Lagrange-basis SRS built on the GPU (kgs_commit_evals)
     commit_evals: require("./src/backend").commitEvals,
+    // kzg_open_all(pTauFilename, coefs) -> {proofs, evals}: the opening proofs of a polynomial (Montgomery
+    // coefficients) at every point of its domain at once (kgs_kzg_open_all); one of them is checked with
+    // curve.pairingEq(proof, [tau]_2, -(C - y G + z proof), [1]_2)
+    kzg_open_all: require("./src/backend").kzgOpenAll,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

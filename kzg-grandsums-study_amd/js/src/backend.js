@@ -213,6 +213,24 @@ async function commitEvals(pTauFilename, evals) {
     });
 }
 
+// Every opening of the polynomial with the Montgomery coefficients `coefs` (a Uint8Array or a BigBuffer of
+// 32-byte elements) on the smallest domain 2^k that holds them, over the SRS of pTauFilename
+// (kgs_kzg_open_all, FK20: O(n log n) group operations; the SRS side is cached on the device)
+// -> Promise<{proofs: 2^k x 64 B affine LEM, evals: 2^k x 32 B Montgomery}>, entry i for Fr.w[k]^i
+async function kzgOpenAll(pTauFilename, coefs) {
+    const key = path.resolve(pTauFilename);
+    const c = contiguous(coefs);
+    const n = c.byteLength / 32;
+    if (!Number.isInteger(n) || n > (1 << 23)) {
+        throw new Error("kzg_open_all: the coefficients must be at most 2^23 32-byte elements");
+    }
+    const nBits = n > 1 ? Math.ceil(Math.log2(n)) : 0;
+    return withContext(async slot => {
+        await ensureSrs(slot, key, nBits);
+        return load().kzgOpenAll(slot.ctx, c);
+    });
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -265,4 +283,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
