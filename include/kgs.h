@@ -201,6 +201,10 @@ int kgs_srs_zero_points(kgs_ctx_t* ctx, int* zero_points);
 /* Read [tau]_2 (128 B LEM, section 3 offset 128) from a ptau (verifier input,
  * src/grandsum/mset_eq_kzg_verifier.js:18-19). */
 int kgs_ptau_read_tau_g2(const char* path, uint8_t out128[128]);
+/* Read [tau^k]_2, point k of section 3 (128 B LEM): a ceremony's ptau holds 2^power of them, the synthetic
+ * writer's two ([1]_2 and [tau]_2). KGS_E_IO when the section holds fewer than k + 1 points. k = 1 is
+ * kgs_ptau_read_tau_g2. kgs_kzg_verify_coset takes [tau^l]_2. */
+int kgs_ptau_read_tau_g2_pow(const char* path, uint64_t k, uint8_t out128[128]);
 
 /* Write a synthetic ptau (sections 1-3 with the hermez layout; section 3 holds [1]_2 and
  * [tau]_2 only) for a known tau (32 B LE standard form). G1 powers are generated on the GPU of
@@ -660,6 +664,58 @@ int kgs_kzg_open_all_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t le
  * and a z or y that is not below r), KGS_E_ARG for a NULL argument or a tau_g2 off its curve. */
 int kgs_kzg_verify(const uint8_t commit_lem[64], const uint8_t z_mont[32], const uint8_t y_mont[32],
                    const uint8_t proof_lem[64], const uint8_t tau_g2[128]);
+/* Column sums of per-point products: out_lem[i] = sum_{r < rows} s_{r cols + i} * P_{r cols + i} for i < cols
+ * (the pointwise step of kgs_kzg_open_cosets as a primitive): signed-digit double-and-add, from
+ * 2^17 terms on with two rows of a column per lane sharing their doublings, the rows summed in extended coordinates
+ * (equal, opposite and identity terms are summed correctly), one batched affine conversion of cols points.
+ *   points_lem   rows * cols affine LEM points, row after row; 64 zero bytes is the identity; NOT validated
+ *   scalars_std  rows * cols x 32 B little-endian STANDARD form; any 256-bit integer, taken mod r
+ *   rows, cols   rows >= 1 (any integer), rows * cols <= 2^26; cols == 0 does nothing
+ *   out_lem      cols canonical affine LEM points (64 zero bytes for the identity); must not overlap the inputs
+ * ctx == NULL computes on the host (no GPU is touched). Failures: KGS_E_ARG for rows == 0, more than 2^26
+ * terms, a NULL buffer with cols > 0, a context attached to a rank group or with MSM sharding on. Context
+ * contract as for kgs_g1_mul_each: own device buffers (128 B per term), no SRS, nothing of the prover's
+ * touched, idle on return, on error paths too. */
+int kgs_g1_mul_sum(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t rows, uint64_t cols,
+                   uint8_t* out_lem);
+/* Same with device pointers (on ctx's device; ctx must not be NULL). The inputs are only read. */
+int kgs_g1_mul_sum_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t rows,
+                          uint64_t cols, void* d_out_lem);
+/* Every coset opening of one polynomial at once. With n = 2^nbits, l = 2^lbits, m = n / l and
+ * w = Fr.w[nbits], coset i < m is H_i = { w^(i + m j) : j < l }, the zeros of X^l - a_i with a_i = w^(i l), and
+ * proofs_lem[i] = [q_i(tau)]_1 for p = q_i (X^l - a_i) + I_i, deg I_i < l: one 64 B proof for the l values
+ * p(w^(i + m j)) = evals[i + m j]. lbits = 0 is kgs_kzg_open_all (same bytes); lbits = nbits gives one
+ * identity. The Toeplitz product of kgs_kzg_open_all splits into l products of size m over the stride-l
+ * subsequences of the coefficients and of the SRS: l zero-padded Fr transforms of size 2m, one multiply-sum
+ * pass of 2n terms into 2m points (kgs_g1_mul_sum), ONE unscaled inverse G1 transform of size 2m and a
+ * forward one of size m. The SRS side (the l G1 transforms of size 2m, scaled by 1 / 2m, 128 B x 2^nbits) is
+ * built as one partial transform of size 2n on first use and cached per (SRS, nbits, lbits) under the rules
+ * of kgs_kzg_open_all's row.
+ *   coef_mont   len <= 2^nbits coefficients, 32 B Montgomery each (len == 0: identities and zero evaluations)
+ *   nbits       0 .. min(23, the nbits_max the SRS was loaded for);  lbits  0 .. nbits
+ *   proofs_lem  2^(nbits - lbits) canonical affine LEM points, the identity as 64 zero bytes
+ *   evals_mont  NULL, or 2^nbits x 32 B that receive p(w^k) in natural order, as kgs_kzg_open_all gives them
+ * Failures, context contract and what the call may grow: as for kgs_kzg_open_all (KGS_E_SRS "no SRS loaded";
+ * KGS_E_ARG for nbits or lbits out of range, len > 2^nbits, a NULL buffer with work to do, a rank group, MSM
+ * sharding, an SRS slice). It leaves kgs_kzg_open_all's rows and the Lagrange cache as they are. */
+int kgs_kzg_open_cosets(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, int nbits, int lbits, uint8_t* proofs_lem,
+                        uint8_t* evals_mont);
+/* Same with device pointers (on ctx's device); d_coef_mont is only read. */
+int kgs_kzg_open_cosets_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int lbits,
+                               void* d_proofs_lem, void* d_evals_mont);
+/* 1 when the SRS side of kgs_kzg_open_cosets for (nbits, lbits) is cached on the device for ctx's SRS (lbits
+ * = 0: kgs_kzg_open_all's row), else 0: such a call builds nothing. No GPU work. */
+int kgs_kzg_open_cosets_cached(kgs_ctx_t* ctx, int nbits, int lbits);
+/* Host only (no GPU, no context): the check of one coset opening of kgs_kzg_open_cosets,
+ * e(-proof, [tau^l]_2) e(C - [I(tau)]_1 + a_i proof, [1]_2) == 1, where I interpolates the l values
+ * ys_mont[j] = p(w^(index + m j)): I = sum_k d_k X^k with d_k = w^(-index k) J_k and J the inverse transform
+ * of size l of the values (kgs_ntt's convention); [I(tau)]_1 is the host sum of kgs_msm_points over
+ * srs_g1_lem, the first l points [tau^k]_1 of the SRS (affine LEM). nbits 0 .. 28, lbits 0 .. nbits,
+ * index < 2^(nbits - lbits). Returns 1 valid, 0 invalid (which includes a commitment, proof or SRS point
+ * that is no canonical point of the curve and a value that is not below r), KGS_E_ARG for a NULL argument,
+ * a range error or a tau_l_g2 off its curve. */
+int kgs_kzg_verify_coset(const uint8_t commit_lem[64], int nbits, int lbits, uint64_t index, const uint8_t* ys_mont,
+                         const uint8_t proof_lem[64], const uint8_t* srs_g1_lem, const uint8_t tau_l_g2[128]);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -686,6 +742,15 @@ int kgs_bench_g1_ntt(kgs_ctx_t* ctx, const void* d_in, void* d_out, int logm, in
  * 2 the pointwise pass alone (2^(nbits + 1) per-lane multiplications and their affine conversion). */
 int kgs_bench_kzg_open_all(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int what, int reps,
                            double* ms);
+/* `reps` runs of a leg of kgs_kzg_open_cosets_device (1 <= lbits < nbits, 1 <= len <= 2^nbits), as
+ * kgs_bench_kzg_open_all times its own. what: 0 the call with the cache warm, 1 the build of the cached rows
+ * (the partial transform and its scaling, not published), 2 the multiply-sum pass alone (2^(nbits + 1) terms
+ * into 2m points and their affine conversion), 3 the two G1 transforms alone (the inverse of size 2m and the
+ * forward of size m, over the call's own u and h), 4 kgs_g1_mul_each's kernel over the same 2^(nbits + 1)
+ * terms, no sum and no conversion; 5 the multiply-sum pass with one row per lane (that kernel, then the column
+ * sums: the other arm of the A/B of DESIGN.md §20; what 2 runs the pass as it ships, two rows per lane). */
+int kgs_bench_kzg_open_cosets(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int lbits, int what,
+                              int reps, double* ms);
 /* The route kgs_commit_evals_device replaces, with the same device-resident input: to Montgomery form,
  * inverse NTT, kgs_msm over the resident window tables (profiles/g1_ntt_time.py times both by the wall
  * clock; each ends synchronised). */

@@ -184,6 +184,17 @@ def lib():
         L.kgs_kzg_open_all_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                               ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_kzg_verify.argtypes = [c_u8p, c_u8p, c_u8p, c_u8p, c_u8p]
+        L.kgs_g1_mul_sum.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64, ctypes.c_uint64, c_u8p]
+        L.kgs_g1_mul_sum_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                            ctypes.c_uint64, ctypes.c_void_p]
+        L.kgs_kzg_open_cosets.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, c_u8p,
+                                          c_u8p]
+        L.kgs_kzg_open_cosets_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.kgs_kzg_open_cosets_cached.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.kgs_kzg_verify_coset.argtypes = [c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, c_u8p, c_u8p, c_u8p,
+                                           c_u8p]
+        L.kgs_ptau_read_tau_g2_pow.argtypes = [ctypes.c_char_p, ctypes.c_uint64, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.kgs_ctx_set_reference_quirks.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -808,6 +819,44 @@ class Context:
         Montgomery coefficients, read only; d_proofs to 2^nbits x 64 writable bytes; d_evals to 2^nbits x
         32 writable bytes, or None."""
         _check(lib().kgs_kzg_open_all_device(self._h, d_coef, n, nbits, d_proofs, d_evals))
+
+    def g1_mul_sum(self, points_lem, scalars_std, rows):
+        """Column sums of per-point products on the GPU (kgs_g1_mul_sum): see the module-level g1_mul_sum."""
+        return _g1_mul_sum(self._h, points_lem, scalars_std, rows)
+
+    def g1_mul_sum_device(self, d_points, d_scalars, rows, cols, d_out):
+        """Device-resident twin (kgs_g1_mul_sum_device): device pointers (ints) to rows * cols affine LEM
+        points of 64 B and as many standard-form scalars of 32 B, both only read, and cols x 64 writable bytes."""
+        _check(lib().kgs_g1_mul_sum_device(self._h, d_points, d_scalars, rows, cols, d_out))
+
+    def kzg_open_cosets(self, coef_mont, nbits, lbits, evals=False):
+        """Every coset opening of a polynomial at once (kgs_kzg_open_cosets): with n = 2^nbits, l = 2^lbits
+        and m = n / l, entry i < m of the result is the one 64 B proof for the l values p(w^(i + m j)), j < l,
+        on the coset w^i <w^m> (w = Fr.w[nbits]). coef_mont: at most 2^nbits Montgomery coefficients of
+        32 B. lbits = 0 is kzg_open_all. The SRS side is built on first use and cached on the device per (SRS,
+        nbits, lbits). Returns m x 64 B affine LEM, or with evals=True the pair (proofs, p(w^k) in natural
+        order as 2^nbits x 32 B Montgomery)."""
+        if len(coef_mont) % 32:
+            raise ValueError("coef_mont must hold 32-byte elements")
+        n = len(coef_mont) // 32
+        ok = 0 <= nbits <= 23 and 0 <= lbits <= nbits  # else the library refuses before it writes
+        proofs = ctypes.create_string_buffer(64 << (nbits - lbits) if ok else 64)
+        ev = ctypes.create_string_buffer(32 << nbits if ok else 32) if evals else None
+        pc, kc = _ptr(coef_mont) if n else (None, None)  # read in place
+        _check(lib().kgs_kzg_open_cosets(self._h, pc, n, nbits, lbits, proofs, ev))
+        del kc
+        return (proofs.raw, ev.raw) if evals else proofs.raw
+
+    def kzg_open_cosets_cached(self, nbits, lbits):
+        """True when the SRS side for (nbits, lbits) is cached on the device (kgs_kzg_open_cosets_cached): a
+        call with these sizes builds nothing. lbits = 0 asks for kzg_open_all's row."""
+        return _check(lib().kgs_kzg_open_cosets_cached(self._h, nbits, lbits)) == 1
+
+    def kzg_open_cosets_device(self, d_coef, n, nbits, lbits, d_proofs, d_evals=None):
+        """Device-resident twin (kgs_kzg_open_cosets_device): d_coef is a device pointer (int) to n <= 2^nbits
+        Montgomery coefficients, read only; d_proofs to 2^(nbits - lbits) x 64 writable bytes; d_evals to
+        2^nbits x 32 writable bytes, or None."""
+        _check(lib().kgs_kzg_open_cosets_device(self._h, d_coef, n, nbits, lbits, d_proofs, d_evals))
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1437,6 +1486,63 @@ def kzg_verify(tau_g2, commit, z_mont, y_mont, proof):
         _check(lib().kgs_ptau_read_tau_g2(os.fsencode(tau_g2), t2))
         tau_g2 = t2.raw
     return _check(lib().kgs_kzg_verify(_buf(commit), _buf(z_mont), _buf(y_mont), _buf(proof), _buf(tau_g2))) == 1
+
+
+def _g1_mul_sum(handle, points_lem, scalars_std, rows):
+    n = len(points_lem) // 64
+    if len(points_lem) % 64 or len(scalars_std) % 32 or n != len(scalars_std) // 32 or rows < 1 or n % rows:
+        raise ValueError("points_lem / scalars_std must hold the same rows * cols 64 B points / 32 B scalars")
+    cols = n // rows
+    out = ctypes.create_string_buffer(max(64 * cols, 1))
+    (pp, kp), (ps, ks) = _ptr(points_lem), _ptr(scalars_std)  # read in place
+    _check(lib().kgs_g1_mul_sum(handle, pp if n else None, ps if n else None, rows, cols, out))
+    del kp, ks
+    return out.raw[:64 * cols]
+
+
+def g1_mul_sum(points_lem, scalars_std, rows, device=0):
+    """out[i] = sum_{r < rows} scalars[r cols + i] * points[r cols + i] (kgs_g1_mul_sum), cols = the number of
+    terms / rows: points 64 B affine LEM (the zero point allowed, not validated), scalars 32 B little-endian
+    standard form (any 256-bit integer, taken mod r). Returns cols x 64 B canonical affine LEM (zeros for the
+    identity). device=None computes on the host."""
+    handle = None if device is None else _context(device).handle
+    return _g1_mul_sum(handle, points_lem, scalars_std, rows)
+
+
+def kzg_open_cosets(pTauFilename, coefs, lbits, device=0):
+    """Every coset opening of the polynomial with the Montgomery coefficients `coefs` on the smallest domain
+    2^nbits that holds them and 2^lbits points, over the SRS of pTauFilename (kgs_kzg_open_cosets): returns
+    (proofs, evals), 2^(nbits - lbits) x 64 B affine LEM, proof i for the values evals[i + 2^(nbits - lbits) j],
+    and 2^nbits x 32 B Montgomery."""
+    if len(coefs) % 32:
+        raise ValueError("coefs must hold 32-byte elements")
+    nbits = max(max(len(coefs) // 32 - 1, 0).bit_length(), lbits)
+    ctx = _context(device)
+    ctx.load_ptau(pTauFilename, nbits)
+    return ctx.kzg_open_cosets(coefs, nbits, lbits, evals=True)
+
+
+def ptau_read_tau_g2_pow(pTauFilename, k):
+    """[tau^k]_2, point k of the ptau's section 3, as 128 B LEM (kgs_ptau_read_tau_g2_pow); a file that holds
+    fewer points raises KgsError (KGS_E_IO)."""
+    out = ctypes.create_string_buffer(128)
+    _check(lib().kgs_ptau_read_tau_g2_pow(os.fsencode(pTauFilename), k, out))
+    return out.raw
+
+
+def kzg_verify_coset(tau_l_g2, srs_g1, commit, nbits, lbits, index, ys_mont, proof):
+    """The check of one coset opening on the host (kgs_kzg_verify_coset): proof opens commit to the 2^lbits
+    values ys_mont (32 B Montgomery each, ys[j] = p(w^(index + m j)), m = 2^(nbits - lbits)) on coset
+    `index`. tau_l_g2: [tau^l]_2 as 128 B LEM, or the name of a ptau file to read it from; srs_g1: the first
+    2^lbits points [tau^k]_1 as 64 B affine LEM (more are ignored). Returns a bool; a point off the curve or
+    a value not below r is False."""
+    l = 1 << lbits if 0 <= lbits <= 28 else 0
+    if len(commit) != 64 or len(proof) != 64 or len(ys_mont) != 32 * l or len(srs_g1) < 64 * l:
+        raise ValueError("commit / proof hold 64 bytes, ys_mont 2^lbits x 32, srs_g1 at least 2^lbits x 64")
+    if isinstance(tau_l_g2, (str, os.PathLike)) or len(tau_l_g2) != 128:
+        tau_l_g2 = ptau_read_tau_g2_pow(tau_l_g2, l)
+    return _check(lib().kgs_kzg_verify_coset(_buf(commit), nbits, lbits, index, _buf(ys_mont), _buf(proof),
+                                             _buf(srs_g1[:64 * l]), _buf(tau_l_g2))) == 1
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

@@ -139,6 +139,10 @@ struct SrsTables {
   // outside it and published complete, released with the tables
   std::map<int, std::shared_ptr<LagrangeRow>> lagrange;
   std::map<int, std::shared_ptr<FkRow>> fk;  // nbits -> kgs_kzg_open_all's row, under the same rules
+  // (nbits, lbits >= 1) -> kgs_kzg_open_cosets' rows (g1_ntt.cpp), under the same rules: the
+  // l = 2^lbits transforms of size 2m = 2n / l of the stride-l subsequences of the SRS side, scaled by 1 / 2m,
+  // 2n points in all; block b of 2m points belongs to the residue bitrev_l(b)
+  std::map<std::pair<int, int>, std::shared_ptr<FkRow>> fk_cosets;
   ~SrsTables() {
     if (tb.table) {
       hipSetDevice(device);

@@ -318,6 +318,190 @@ int kzg_open_all_entry(kgs_ctx_t* ctx, const void* coef, uint64_t len, int nbits
   API_END
 }
 
+// ------------------------------------------------------------------ coset openings
+// The rows of (the context's SRS, nbits, lbits >= 1, m = n / l >= 2), enqueued on the main stream and not yet
+// published. X_{j l + r} = x^(r)_j = s_{(m-2-j) l + r} for j <= m - 2 and the identity above: the first n - l
+// points of table row 0 with their blocks of l reversed. The l transforms of size 2m of the stride-l
+// subsequences of X are the first log2(2m) stages of the transform of size 2n (g1_ntt_run, `stages`), then
+// one uniform scaling by 1 / 2m. Block b of the result holds the row of residue bitrev_l(b): kzg_open_cosets_run
+// lays the Fr side out in the same order (launch_coset_rows). Row 0's rho stays on the points, as in fk_build.
+std::shared_ptr<FkRow> coset_build(kgs_ctx& c, int nbits, int lbits) {
+  const uint64_t n = 1ull << nbits, l = 1ull << lbits;
+  auto row = std::make_shared<FkRow>();
+  row->device = c.device;
+  row->n = n;
+  HC(dev_malloc((void**)&row->xhat, 128 * n));
+  uint32_t* x = c.buf("gn_io", 128 * n);
+  HC(hipMemsetAsync(x, 0, 128 * n, c.st));
+  launch_g1_from29(c.st, x, c.tb.table, n - l, true, lbits);
+  const int logm2 = nbits - lbits + 1;
+  const G1NttWork w = ntt_work(c, nbits + 1);
+  uint32_t root[8], sc[8];
+  fr_words(ntt_root(nbits + 1, false), root);
+  fr_words(ninv_std(logm2), sc);
+  g1_ntt_run(c.st, w, row->xhat, x, nbits + 1, root, sc, G1NTT_MAP_AUTO, logm2);
+  check_launch();
+  return row;
+}
+
+// The cached rows, built on first use under the Lagrange row's rules (lagrange_row, fk_row)
+std::shared_ptr<FkRow> coset_row(kgs_ctx& c, int nbits, int lbits) {
+  const std::pair<int, int> key(nbits, lbits);
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    auto it = c.srs->fk_cosets.find(key);
+    if (it != c.srs->fk_cosets.end()) return it->second;
+  }
+  DrainOnError drain(&c);
+  const std::shared_ptr<FkRow> row = coset_build(c, nbits, lbits);
+  HC(hipStreamSynchronize(c.st));
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  auto& slot = c.srs->fk_cosets[key];
+  if (!slot) slot = row;  // else: built concurrently by another context and published first; ours is released
+  return slot;
+}
+
+// u^_i = sum_r (the Fr transforms' output words)_{r, i} x (the cached points)_{r, i}, i < 2m, affine, into w.aff
+void coset_pointwise(kgs_ctx& c, const G1NttWork& w, const FkRow& row, const uint32_t* chat_words, int lbits,
+                     int group = G1_MUL_SUM_GROUP) {
+  const uint64_t cols = (2 * row.n) >> lbits;
+  launch_g1_mul_sum(c.st, w.xyzz, row.xhat, chat_words, 1ull << lbits, cols, false, group);
+  launch_batch_affine(c.st, w.aff, w.xyzz, w.scratch, cols);
+}
+
+// the two G1 transforms of a coset call: u = the unscaled inverse of size 2m in place in w.aff, h = u_{m-1 ..
+// 2m-3} and one identity, the forward transform of size m of h into d_proofs
+void coset_transforms(kgs_ctx& c, const G1NttWork& w, int logm, uint32_t* h, uint32_t* d_proofs) {
+  const uint64_t m = 1ull << logm;
+  uint32_t root[8];
+  fr_words(ntt_root(logm + 1, true), root);
+  g1_ntt_run(c.st, w, w.aff, w.aff, logm + 1, root, nullptr, G1NTT_MAP_AUTO);
+  HC(hipMemcpyAsync(h, w.aff + 16 * (m - 1), 64 * (m - 1), hipMemcpyDeviceToDevice, c.st));
+  HC(hipMemsetAsync(h + 16 * (m - 1), 0, 64, c.st));
+  fr_words(ntt_root(logm, false), root);
+  g1_ntt_run(c.st, w, d_proofs, h, logm, root, nullptr, G1NTT_MAP_AUTO);
+}
+
+// All m = 2^(nbits - lbits) coset openings (kgs.h kgs_kzg_open_cosets) of the polynomial with the `len` <= n
+// Montgomery coefficients at d_coef (device), enqueued on the main stream (not synchronised). lbits = 0 is
+// kzg_open_all_run. The caller holds the context, has checked it and reset its staging.
+void kzg_open_cosets_run(kgs_ctx& c, const uint32_t* d_coef, uint64_t len, int nbits, int lbits, uint32_t* d_proofs,
+                         uint32_t* d_evals) {
+  if (!lbits) return kzg_open_all_run(c, d_coef, len, nbits, d_proofs, d_evals);
+  const uint64_t n = 1ull << nbits, l = 1ull << lbits, m = n >> lbits;
+  const int logm = nbits - lbits;
+  if (!len) {  // the zero polynomial
+    HC(hipMemsetAsync(d_proofs, 0, 64 * m, c.st));
+    if (d_evals) HC(hipMemsetAsync(d_evals, 0, 32 * n, c.st));
+    return;
+  }
+  uint32_t* sa = c.buf("fk_fr", 64 * n);
+  if (m == 1) {  // one coset, the whole domain: p = I, the quotient is zero
+    HC(hipMemsetAsync(d_proofs, 0, 64, c.st));
+  } else {
+    const std::shared_ptr<FkRow> row = coset_row(c, nbits, lbits);
+    if (logm + 1 > c.logM) ensure_domain(c, logm + 1);
+    uint32_t* rows = c.buf("fk_rows", 32 * n);
+    uint32_t* sb = c.buf("fk_chat", 64 * n);
+    uint32_t* h = c.buf("fk_h", 64 * m);
+    const G1NttWork w = ntt_work(c, nbits + 1);  // xyzz holds the 2n products; serves both transforms too
+    // row b of the Fr side = the coefficients of residue bitrev_l(b), the order of the cached rows' blocks
+    launch_coset_rows(c.st, rows, d_coef, len, logm, lbits);
+    for (uint64_t b = 0; b < l; b++)  // c^ = the l zero-padded Fr transforms of size 2m
+      ntt_dif(c.st, sa + 16 * m * b, rows + 8 * m * b, m, logm + 1, nullptr, c.tw_fwd, c.logM);
+    launch_bitrev_blocks(c.st, sb, sa, logm + 1, l);
+    coset_pointwise(c, w, *row, sb, lbits);
+    coset_transforms(c, w, logm, h, d_proofs);
+  }
+  if (d_evals) {
+    if (nbits > c.logM) ensure_domain(c, nbits);
+    ntt_dif(c.st, sa, d_coef, len, nbits, nullptr, c.tw_fwd, c.logM);
+    launch_bitrev_copy(c.st, d_evals, sa, nbits);
+  }
+  check_launch();
+}
+
+int kzg_open_cosets_entry(kgs_ctx_t* ctx, const void* coef, uint64_t len, int nbits, int lbits, void* proofs, void* evals,
+                          bool device) {
+  API_BEGIN
+  const char* fn = "kgs_kzg_open_cosets";
+  if (!ctx) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL ctx");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_open_all(*ctx, nbits, fn);
+  if (lbits < 0 || lbits > nbits)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": lbits must be in 0 .. nbits = " + std::to_string(nbits));
+  const uint64_t n = 1ull << nbits, m = n >> lbits;
+  if (len > n)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": len = " + std::to_string(len) + " coefficients do not fit the domain of 2^" +
+                                  std::to_string(nbits) + " points.");
+  if (!proofs || (len && !coef)) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  if (device) {
+    kzg_open_cosets_run(c, (const uint32_t*)coef, len, nbits, lbits, (uint32_t*)proofs, (uint32_t*)evals);
+  } else {
+    uint32_t* dc = c.buf("fk_coef", 32 * (len ? len : 1));
+    uint32_t* dp = c.buf("fk_out", 64 * m);
+    uint32_t* de = evals ? c.buf("fk_ev", 32 * n) : nullptr;
+    if (len) HC(hipMemcpyAsync(dc, coef, 32 * len, hipMemcpyHostToDevice, c.st));
+    kzg_open_cosets_run(c, dc, len, nbits, lbits, dp, de);
+    HC(hipMemcpyAsync(proofs, dp, 64 * m, hipMemcpyDeviceToHost, c.st));
+    if (evals) HC(hipMemcpyAsync(evals, de, 32 * n, hipMemcpyDeviceToHost, c.st));
+  }
+  c.reset_staging();
+  API_END
+}
+
+int g1_mul_sum_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, uint64_t rows, uint64_t cols, void* out,
+                     bool device) {
+  API_BEGIN
+  const char* fn = "kgs_g1_mul_sum";
+  if (!rows) throw KgsError(KGS_E_ARG, std::string(fn) + ": rows must be at least 1");
+  if (rows > G1_MUL_EACH_MAX || cols > G1_MUL_EACH_MAX || rows * cols > G1_MUL_EACH_MAX)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": at most 2^26 terms");
+  if (cols && (!points || !scalars || !out)) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (!ctx) {
+    if (device) throw KgsError(KGS_E_ARG, "kgs_g1_mul_sum_device: NULL ctx");
+    std::vector<uint8_t> p(64 * rows), s(32 * rows);
+    for (uint64_t i = 0; i < cols; i++) {  // a column's terms side by side, then the host MSM's segment sum
+      for (uint64_t r = 0; r < rows; r++) {
+        memcpy(p.data() + 64 * r, (const uint8_t*)points + 64 * (r * cols + i), 64);
+        memcpy(s.data() + 32 * r, (const uint8_t*)scalars + 32 * (r * cols + i), 32);
+      }
+      host::g1_lincomb_segment(p.data(), s.data(), rows).to_affine_lem((uint8_t*)out + 64 * i);
+    }
+    return KGS_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_ctx(*ctx, fn);
+  if (!cols) return KGS_OK;
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  const uint64_t n = rows * cols;
+  uint32_t* xyzz = c.buf("gn_xyzz", 128 * n);
+  uint32_t* scratch = c.buf("gn_scratch", 32 * cols);
+  const uint32_t *dp = (const uint32_t*)points, *ds = (const uint32_t*)scalars;
+  uint32_t* dout = (uint32_t*)out;
+  if (!device) {
+    uint32_t* io = c.buf("gn_io", 64 * n);
+    uint32_t* sc = c.buf("fk_chat", 32 * n);
+    HC(hipMemcpyAsync(io, points, 64 * n, hipMemcpyHostToDevice, c.st));
+    HC(hipMemcpyAsync(sc, scalars, 32 * n, hipMemcpyHostToDevice, c.st));
+    dp = io;
+    ds = sc;
+    dout = c.buf("fk_out", 64 * cols);
+  }
+  launch_g1_mul_sum(c.st, xyzz, dp, ds, rows, cols, true);
+  launch_batch_affine(c.st, dout, xyzz, scratch, cols);
+  check_launch();
+  if (!device) HC(hipMemcpyAsync(out, dout, 64 * cols, hipMemcpyDeviceToHost, c.st));
+  HC(hipStreamSynchronize(c.st));
+  API_END
+}
+
 int g1_mul_each_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, uint64_t n, void* out, bool device) {
   API_BEGIN
   const char* fn = "kgs_g1_mul_each";
@@ -429,6 +613,36 @@ int kgs_kzg_open_all_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t le
   return kzg_open_all_entry(ctx, d_coef_mont, len, nbits, d_proofs_lem, d_evals_mont, true);
 }
 
+int kgs_kzg_open_cosets(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t len, int nbits, int lbits, uint8_t* proofs_lem,
+                        uint8_t* evals_mont) {
+  return kzg_open_cosets_entry(ctx, coef_mont, len, nbits, lbits, proofs_lem, evals_mont, false);
+}
+
+int kgs_kzg_open_cosets_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int lbits,
+                               void* d_proofs_lem, void* d_evals_mont) {
+  return kzg_open_cosets_entry(ctx, d_coef_mont, len, nbits, lbits, d_proofs_lem, d_evals_mont, true);
+}
+
+int kgs_kzg_open_cosets_cached(kgs_ctx_t* ctx, int nbits, int lbits) {
+  API_BEGIN
+  if (!ctx) throw KgsError(KGS_E_ARG, "kgs_kzg_open_cosets_cached: NULL ctx");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!ctx->srs) return 0;
+  std::lock_guard<std::mutex> reg(g_reg_mu);
+  return lbits ? (int)ctx->srs->fk_cosets.count({nbits, lbits}) : (int)ctx->srs->fk.count(nbits);
+  API_END
+}
+
+int kgs_g1_mul_sum(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t rows, uint64_t cols,
+                   uint8_t* out_lem) {
+  return g1_mul_sum_entry(ctx, points_lem, scalars_std, rows, cols, out_lem, false);
+}
+
+int kgs_g1_mul_sum_device(kgs_ctx_t* ctx, const void* d_points_lem, const void* d_scalars_std, uint64_t rows,
+                          uint64_t cols, void* d_out_lem) {
+  return g1_mul_sum_entry(ctx, d_points_lem, d_scalars_std, rows, cols, d_out_lem, true);
+}
+
 int kgs_g1_ntt(kgs_ctx_t* ctx, const uint8_t* points_lem, uint8_t* out_lem, int logm, int inverse) {
   return g1_ntt_entry(ctx, points_lem, out_lem, false, logm, inverse);
 }
@@ -537,6 +751,62 @@ int kgs_bench_kzg_open_all(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len
       built = fk_build(c, nbits);
     else
       fk_pointwise(c, w, *row, chat);
+    HC(hipEventRecord(e1, c.st));
+    check_launch();
+    HC(hipEventSynchronize(e1));
+    float f = 0;
+    HC(hipEventElapsedTime(&f, e0, e1));
+    ms[r] = f;
+  }
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  c.reset_staging();
+  API_END
+}
+
+// ---- timing helper of profiles/kzg_open_cosets_time.py
+int kgs_bench_kzg_open_cosets(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int lbits, int what,
+                              int reps, double* ms) {
+  API_BEGIN
+  const char* fn = "kgs_bench_kzg_open_cosets";
+  if (!ctx || !d_coef_mont || !ms) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (what < 0 || what > 5 || reps < 1) throw KgsError(KGS_E_ARG, std::string(fn) + ": bad what / reps");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_open_all(*ctx, nbits, fn);
+  if (lbits < 1 || lbits >= nbits) throw KgsError(KGS_E_ARG, std::string(fn) + ": lbits must be in 1 .. nbits - 1");
+  const uint64_t n = 1ull << nbits, m = n >> lbits;
+  if (len < 1 || len > n) throw KgsError(KGS_E_ARG, std::string(fn) + ": len must be in 1 .. 2^nbits");
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  uint32_t* out = c.buf("fk_out", 64 * m);
+  // every leg after one whole call: the rows cached, the buffers grown, c^ in "fk_chat", u in "gn_aff" and h
+  // in "fk_h" (the operands the transform legs run over: points of this polynomial, no periodic vector)
+  kzg_open_cosets_run(c, (const uint32_t*)d_coef_mont, len, nbits, lbits, out, nullptr);
+  HC(hipStreamSynchronize(c.st));
+  const std::shared_ptr<FkRow> row = coset_row(c, nbits, lbits);
+  const G1NttWork w = ntt_work(c, nbits + 1);
+  const uint32_t* chat = c.buf("fk_chat", 64 * n);
+  uint32_t* h = c.buf("fk_h", 64 * m);
+  hipEvent_t e0, e1;
+  HC(hipEventCreate(&e0));
+  HC(hipEventCreate(&e1));
+  for (int r = 0; r < reps; r++) {
+    std::shared_ptr<FkRow> built;
+    HC(hipEventRecord(e0, c.st));
+    if (what == 0)
+      kzg_open_cosets_run(c, (const uint32_t*)d_coef_mont, len, nbits, lbits, out, nullptr);
+    else if (what == 1)
+      built = coset_build(c, nbits, lbits);
+    else if (what == 2)
+      coset_pointwise(c, w, *row, chat, lbits);
+    else if (what == 3)
+      coset_transforms(c, w, nbits - lbits, h, out);
+    else if (what == 4)
+      launch_g1_mul_each(c.st, w.xyzz, row->xhat, chat, 2 * n, false);
+    else
+      coset_pointwise(c, w, *row, chat, lbits, 1);
     HC(hipEventRecord(e1, c.st));
     check_launch();
     HC(hipEventSynchronize(e1));

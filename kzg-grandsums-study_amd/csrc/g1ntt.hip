@@ -197,17 +197,134 @@ __global__ void __launch_bounds__(64) k_g1_mul_each(uint32_t* __restrict__ out_x
   r.store(out_xyzz + 32 * i);
 }
 
+// out_xyzz[g cols + i] = sum_{j < L} k[(g L + j) cols + i] * in_aff[(g L + j) cols + i]: L rows of a column per
+// lane, sharing the 254 doublings (Straus): 254 (9 + 10 L) field products for L terms against
+// 254 * 19 L. L records do not fit in registers beside the accumulator, so each lane keeps its records in a
+// column of LDS of its own (word-major: lane = bank, no conflicts, no barrier) and reloads a base from global
+// memory at each addition. The last group of a column may hold fewer than L rows. L = 2 ships: 99 VGPRs, 8 KiB
+// of LDS per block, four waves per SIMD, no scratch; 62.4 ms against 79.8 ms for one row per lane at 2^21 terms
+// in 64 rows. L = 4 (16 KiB, three waves) measured 63.6 ms and was dropped. Half the threads doing twice the
+// work each lose where the launch is latency-bound (6.5 ms against 4.0 ms at 2^13 terms, 5.9 against 6.2 at
+// 2^17): launch_g1_mul_sum takes this kernel from G1_MUL_GROUP_MIN_TERMS terms on.
+template <int L, bool REDUCE>
+__global__ void __launch_bounds__(64) k_g1_mul_group(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
+                                                     const uint32_t* __restrict__ sc, uint64_t rows, uint64_t cols,
+                                                     uint64_t ngroups) {
+  KGS_AUX_PRIO();
+  __shared__ uint32_t recs[L][G1NTT_TW_WORDS][64];
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ngroups * cols) return;
+  const uint64_t g = t / cols, i = t - g * cols;
+  const uint32_t lane = threadIdx.x;
+  uint32_t live = 0;  // bit j: row g L + j exists and its point is not the identity
+#pragma unroll 1
+  for (int j = 0; j < L; j++) {
+    const uint64_t r = g * L + j;
+    if (r >= rows) break;
+    fr k = fr::load(sc + 8 * (r * cols + i));
+    if (REDUCE) {
+#pragma unroll 1
+      for (int s = 0; s < 5; s++) k = fr::reduce_once(k);  // 2^256 < 6 r
+    }
+    uint32_t rec[G1NTT_TW_WORDS];
+    naf_record(k.v, rec);
+#pragma unroll
+    for (int w = 0; w < G1NTT_TW_WORDS; w++) recs[j][w][lane] = rec[w];
+    if (!g1_aff::load(in_aff + 16 * (r * cols + i)).is_inf()) live |= 1u << j;
+  }
+  g1_xyzz acc = g1_xyzz::inf();
+  if (live) {
+#pragma unroll 1
+    for (int d = 255; d >= 0; d--) {
+      acc = acc.dbl();
+      const int w = d >> 5, bit = d & 31;
+#pragma unroll 1
+      for (int j = 0; j < L; j++) {
+        if (!((live >> j) & 1u)) continue;
+        const uint32_t p = (recs[j][w][lane] >> bit) & 1u, m = (recs[j][8 + w][lane] >> bit) & 1u;
+        if (p | m) {
+          g1_aff s = g1_aff::load(in_aff + 16 * ((g * L + j) * cols + i));
+          if (m) s.y = s.y.neg();
+          acc.add_aff(s);
+        }
+      }
+    }
+  }
+  acc.store(out_xyzz + 32 * (g * cols + i));
+}
+
+// The column sums of kgs_g1_mul_sum / kgs_kzg_open_cosets over the rows x cols products
+// k_g1_mul_each left in xyzz, in place and by eights: of the rows that are still live (the multiples of
+// `stride`) thread (g, i) adds rows (8 g + j) stride, j < 8, of column i into row 8 g stride, its group's
+// first, which no other thread reads or writes; the next pass runs with 8 stride, and row 0 ends as the
+// sum. Adjacent lanes take adjacent columns. The terms of a column may be equal (equal rows of the SRS side
+// under equal coefficients), opposite or the identity: g1_xyzz::add branches on all three. Against the 254
+// doublings and ~254 additions per term in k_g1_mul_each this is one addition per term, under 1 % of the
+// products.
+constexpr int G1_SUM_FAN = 8;
+__global__ void __launch_bounds__(64) k_g1_col_sum(uint32_t* __restrict__ xyzz, uint64_t rows, uint64_t cols, uint64_t stride,
+                                                   uint64_t ngroups) {
+  KGS_AUX_PRIO();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ngroups * cols) return;
+  const uint64_t g = t / cols, i = t - g * cols;
+  const uint64_t r0 = g * G1_SUM_FAN * stride;
+  g1_xyzz acc = g1_xyzz::load(xyzz + 32 * (r0 * cols + i));
+#pragma unroll 1
+  for (int j = 1; j < G1_SUM_FAN; j++) {
+    const uint64_t r = r0 + (uint64_t)j * stride;
+    if (r >= rows) break;
+    acc.add(g1_xyzz::load(xyzz + 32 * (r * cols + i)));
+  }
+  acc.store(xyzz + 32 * (r0 * cols + i));
+}
+
+// out[b m + u] = in[u l + bitrev_l(b)] (8 words each), zero from index len on; m = 2^logm, l = 2^lbits >= 2
+__global__ void __launch_bounds__(256) k_coset_rows(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, uint64_t len,
+                                                    int logm, int lbits) {
+  KGS_AUX_PRIO();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >> (logm + lbits)) return;
+  const uint64_t b = t >> logm, u = t & ((1ull << logm) - 1);
+  const uint64_t src = (u << lbits) | (__brev((uint32_t)b) >> (32 - lbits));
+  uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+  if (src < len) {
+    const uint4* q = reinterpret_cast<const uint4*>(in + 8 * src);
+    lo = q[0];
+    hi = q[1];
+  }
+  uint4* o = reinterpret_cast<uint4*>(out + 8 * t);
+  o[0] = lo;
+  o[1] = hi;
+}
+
+// out[b 2^logm + j] = in[b 2^logm + bitrev(j)] (8 words each), logm >= 1
+__global__ void __launch_bounds__(256) k_bitrev_blocks(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, int logm,
+                                                       uint64_t total) {
+  KGS_AUX_PRIO();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const uint64_t j = t & ((1ull << logm) - 1);
+  const uint64_t src = (t - j) | (__brev((uint32_t)j) >> (32 - logm));
+  const uint4* q = reinterpret_cast<const uint4*>(in + 8 * src);
+  uint4* o = reinterpret_cast<uint4*>(out + 8 * t);
+  o[0] = q[0];
+  o[1] = q[1];
+}
+
 // coordinates x * 2^261 (a table row, k_tab_to29) -> x * 2^256, out of place; nelem = 2 npts coordinates.
-// flip = npts - 1 writes the points in reverse order (0: in order)
+// flip = nblocks - 1 writes the blocks of 2^lb points in reverse order, each in its own order (lb = 0: the
+// points in reverse order); flip = 0: in order
 __global__ void __launch_bounds__(256) k_g1ntt_from29(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
-                                                      uint64_t nelem, G1NttWords c251, uint64_t flip) {
+                                                      uint64_t nelem, G1NttWords c251, uint64_t flip, int lb) {
   KGS_AUX_PRIO();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nelem) return;
   fq c;
 #pragma unroll
   for (int k = 0; k < 8; k++) c.v[k] = c251.w[k];
-  const uint64_t o = flip ? (((flip - (i >> 1)) << 1) | (i & 1)) : i;
+  const uint64_t p = i >> 1;
+  const uint64_t o = flip ? (((((flip - (p >> lb)) << lb) | (p & ((1ull << lb) - 1))) << 1) | (i & 1)) : i;
   (fq::load(in + 8 * i) * c).store(out + 8 * o);
 }
 
@@ -221,12 +338,45 @@ G1NttSizes g1_ntt_sizes(int logn) {
   return z;
 }
 
-void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed) {
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed,
+                      int block_log) {
   G1NttWords c{};
   c.w[7] = 1u << 27;  // 2^251: (x 2^261)(2^251) / 2^256 = x 2^256 in the Montgomery product
   if (npts)
     hipLaunchKernelGGL(k_g1ntt_from29, dim3(nb(2 * npts)), dim3(256), 0, st, out_aff, in29, 2 * npts, c,
-                       reversed ? npts - 1 : (uint64_t)0);
+                       reversed ? (npts >> block_log) - 1 : (uint64_t)0, block_log);
+}
+
+template <int L>
+static void launch_g1_mul_group(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars,
+                                uint64_t rows, uint64_t cols, uint64_t ngroups, bool reduce) {
+  auto* kern = reduce ? k_g1_mul_group<L, true> : k_g1_mul_group<L, false>;
+  hipLaunchKernelGGL(kern, dim3(nb(ngroups * cols, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, rows, cols, ngroups);
+}
+
+void launch_g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t rows,
+                       uint64_t cols, bool reduce, int group) {
+  if (!rows || !cols) return;
+  if (group == 2 && rows > 1 && rows * cols >= G1_MUL_GROUP_MIN_TERMS) {  // two rows per lane, then their sums
+    const uint64_t ngroups = (rows + 1) / 2;
+    launch_g1_mul_group<2>(st, out_xyzz, in_aff, scalars, rows, cols, ngroups, reduce);
+    rows = ngroups;
+  } else {
+    launch_g1_mul_each(st, out_xyzz, in_aff, scalars, rows * cols, reduce);
+  }
+  for (uint64_t stride = 1; stride < rows; stride *= G1_SUM_FAN) {
+    const uint64_t live = (rows + stride - 1) / stride, ngroups = (live + G1_SUM_FAN - 1) / G1_SUM_FAN;
+    hipLaunchKernelGGL(k_g1_col_sum, dim3(nb(ngroups * cols, 64)), dim3(64), 0, st, out_xyzz, rows, cols, stride, ngroups);
+  }
+}
+
+void launch_coset_rows(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t len, int logm, int lbits) {
+  hipLaunchKernelGGL(k_coset_rows, dim3(nb(1ull << (logm + lbits))), dim3(256), 0, st, out, in, len, logm, lbits);
+}
+
+void launch_bitrev_blocks(hipStream_t st, uint32_t* out, const uint32_t* in, int logm, uint64_t nblocks) {
+  const uint64_t total = nblocks << logm;
+  hipLaunchKernelGGL(k_bitrev_blocks, dim3(nb(total)), dim3(256), 0, st, out, in, logm, total);
 }
 
 void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
@@ -246,8 +396,9 @@ void launch_g1_mul_each(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_a
 }
 
 void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,
-                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping) {
+                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping, int stages) {
   const uint64_t n = 1ull << logn, half = n / 2;
+  const int nstages = stages < 0 ? logn : stages;  // fewer: the transforms of the strided subsequences, side by side
   G1NttWords root, scale{};
   for (int j = 0; j < 8; j++) root.w[j] = root_mont[j];
   bool scaled = false;
@@ -259,8 +410,8 @@ void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uin
   }
   hipLaunchKernelGGL(k_g1ntt_twiddles, dim3(nb(half + 1)), dim3(256), 0, st, w.tw, half, root, scale);
   const uint32_t* src = in_aff;
-  for (int logh = 0; logh < logn; logh++) {
-    const bool last = logh == logn - 1;
+  for (int logh = 0; logh < nstages; logh++) {
+    const bool last = logh == nstages - 1;
     const bool uni = mapping == G1NTT_MAP_WAVE || (mapping == G1NTT_MAP_AUTO && logh > 0);
     if (uni && logn - 1 - logh >= 6)
       hipLaunchKernelGGL(k_g1ntt_stage<true>, dim3(nb(half, 64)), dim3(64), 0, st, w.xyzz, src, w.tw, half, logh, logn,

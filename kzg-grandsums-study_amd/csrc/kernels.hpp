@@ -226,8 +226,12 @@ G1NttSizes g1_ntt_sizes(int logn);
 struct G1NttWork {
   uint32_t *xyzz = nullptr, *aff = nullptr, *scratch = nullptr, *tw = nullptr;
 };
+// stages: -1 runs all logn stages. 1 <= stages < logn stops after the stages of half-width 1 .. 2^(stages-1)
+// (DESIGN.md §20): the 2^(logn-stages) blocks of 2^stages consecutive outputs are then the transforms of size
+// 2^stages (root root^(2^(logn-stages))) of the input's subsequences of stride 2^(logn-stages), block b
+// holding the subsequence of residue bitrev(b); scale_std applies to them as to a whole transform.
 void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,
-                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping);
+                const uint32_t root_mont[8], const uint32_t* scale_std, int mapping, int stages = -1);
 // out_aff[i] = scale_std * in_aff[i], i < n: the transform's scaling pass on its own (w sized for n points)
 void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t n,
                      const uint32_t scale_std[8]);
@@ -236,8 +240,28 @@ void launch_g1_scale(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, cons
 // else every k_i < r already (an Fr kernel's output words). in_aff: zeros = identity.
 void launch_g1_mul_each(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t n,
                         bool reduce);
+// out_xyzz[i] = sum_{r < rows} k[r cols + i] * in_aff[r cols + i], i < cols (follow with
+// launch_batch_affine over cols points). out_xyzz holds rows * cols XYZZ points: the products land there
+// (scalars and `reduce` as launch_g1_mul_each takes them) and are summed in place, by eights, into row 0. The
+// sum takes the identity, equal and opposite branches of g1_xyzz::add, the grouped kernel those of add_aff.
+// group: 2, two rows of a column per lane sharing their doublings (k_g1_mul_group; the products then fill
+// the first ceil(rows / 2) rows of out_xyzz), or 1, launch_g1_mul_each over all the terms (what rows == 1 takes,
+// and the other arm of the A/B).
+// Below G1_MUL_GROUP_MIN_TERMS terms (the smallest size at which the grouped kernel measured faster) group 2
+// takes the one-row route as well.
+constexpr int G1_MUL_SUM_GROUP = 2;
+constexpr uint64_t G1_MUL_GROUP_MIN_TERMS = 1ull << 17;
+void launch_g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t rows,
+                       uint64_t cols, bool reduce, int group = G1_MUL_SUM_GROUP);
+// The Fr side of kgs_kzg_open_cosets, l = 2^lbits >= 2 rows of m = 2^logm elements of 8 words:
+// out[b m + u] = in[u l + bitrev_l(b)], zero from index len on (the rows in the cached G1 rows' order)
+void launch_coset_rows(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t len, int logm, int lbits);
+// out[b 2^logm + j] = in[b 2^logm + bitrev(j)], b < nblocks, out of place: launch_bitrev_copy per block
+void launch_bitrev_blocks(hipStream_t st, uint32_t* out, const uint32_t* in, int logm, uint64_t nblocks);
 // npts affine points of a table row (coordinates x * 2^261, msm_points_row29) -> the 2^256 form, out of
-// place; reversed: out_aff[npts - 1 - i] = point i
-void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed = false);
+// place; reversed: out_aff[npts - 1 - i] = point i, or with block_log > 0 the blocks of 2^block_log points
+// in reverse order, each block in its own order (npts a multiple of the block)
+void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed = false,
+                      int block_log = 0);
 
 }  // namespace kgs

@@ -123,4 +123,25 @@ int kgs_ptau_read_tau_g2(const char* path, uint8_t out128[128]) {
   }
 }
 
+int kgs_ptau_read_tau_g2_pow(const char* path, uint64_t k, uint8_t out128[128]) {
+  try {
+    if (!path || !out128) throw KgsError(KGS_E_ARG, "NULL argument");
+    FILE* f = fopen(path, "rb");
+    if (!f) throw KgsError(KGS_E_IO, std::string("cannot open ") + path);
+    std::unique_ptr<FILE, int (*)(FILE*)> guard(f, fclose);
+    PtauInfo info = read_ptau_header(f, path);
+    if (k >= info.s3_size / 128)
+      throw KgsError(KGS_E_IO, "the tauG2 section holds " + std::to_string(info.s3_size / 128) + " points: no [tau^" +
+                                   std::to_string(k) + "]_2");
+    if (fseeko(f, (off_t)(info.s3_pos + 128 * k), SEEK_SET) || fread(out128, 1, 128, f) != 128)
+      throw KgsError(KGS_E_IO, "cannot read [tau^k]_2");
+    return KGS_OK;
+  } catch (const KgsError& e) {
+    return kgs_fail(e);
+  } catch (const std::exception& e) {
+    kgs_errbuf() = e.what();
+    return KGS_E_IO;
+  }
+}
+
 }  // extern "C"

@@ -254,6 +254,60 @@ int kgs_kzg_verify(const uint8_t commit_lem[64], const uint8_t z_mont[32], const
   }
 }
 
+int kgs_kzg_verify_coset(const uint8_t commit_lem[64], int nbits, int lbits, uint64_t index, const uint8_t* ys_mont,
+                         const uint8_t proof_lem[64], const uint8_t* srs_g1_lem, const uint8_t tau_l_g2[128]) {
+  if (!commit_lem || !ys_mont || !proof_lem || !srs_g1_lem || !tau_l_g2) return KGS_E_ARG;
+  if (nbits < 0 || nbits > 28 || lbits < 0 || lbits > nbits || (index >> (nbits - lbits))) return KGS_E_ARG;
+  try {
+    const host::G2A t2 = host::g2_from_lem(tau_l_g2);
+    if (!host::g2_on_curve(t2)) return KGS_E_ARG;
+    const size_t l = (size_t)1 << lbits;
+    if (!host::g1_valid(commit_lem) || !host::g1_valid(proof_lem)) return 0;
+    for (size_t k = 0; k < l; k++)
+      if (!host::g1_valid(srs_g1_lem + 64 * k) || !host::lt_mod(ys_mont + 32 * k, host::FR_MOD.p)) return 0;
+    // J = the inverse transform of size l of y (radix-2, decimation in time, root Fr.w[lbits]^-1, times 1 / l),
+    // then d_k = w^(-i k) J_k: I(X) = sum_k d_k X^k takes the value y_j at w^i psi^j
+    std::vector<Fr> J(l);
+    for (size_t j = 0; j < l; j++) {
+      size_t b = 0;
+      for (int s = 0; s < lbits; s++) b |= ((j >> s) & 1) << (lbits - 1 - s);
+      J[b] = Fr::from_bytes(ys_mont + 32 * j);
+    }
+    const Fr pinv = host::fr_w_cached(lbits).inverse();
+    for (size_t h = 1; h < l; h *= 2) {
+      Fr wh = pinv;
+      for (size_t k = 2 * h; k < l; k *= 2) wh = wh.sqr();
+      Fr tw = Fr::one();
+      for (size_t t = 0; t < h; t++) {
+        for (size_t g = 0; g < l; g += 2 * h) {
+          const Fr a = J[g + t], b = J[g + t + h] * tw;
+          J[g + t] = a + b;
+          J[g + t + h] = a - b;
+        }
+        tw = tw * wh;
+      }
+    }
+    const Fr w = host::fr_w_cached(nbits);
+    const Fr step = w.pow_u64(index).inverse();  // w^(-i)
+    Fr f = Fr::from_u64(l).inverse();
+    std::vector<uint8_t> d(32 * l);
+    for (size_t k = 0; k < l; k++) {
+      uint64_t s[4];
+      (J[k] * f).to_std(s);
+      memcpy(d.data() + 32 * k, s, 32);
+      f = f * step;
+    }
+    const G1 I = host::g1_lincomb_segment(srs_g1_lem, d.data(), l);
+    const Fr a = host::fr_w_cached(nbits - lbits).pow_u64(index);  // a_i = w^(i l)
+    const G1 W = pt(proof_lem);
+    // e(-W, [tau^l]_2) e(C - [I(tau)]_1 + a_i W, [1]_2) == 1
+    const G1 B = pt(commit_lem).add(I.neg()).add(W.mul(a));
+    return host::pairing_eq2(W.neg(), t2, B, host::g2_gen()) ? 1 : 0;
+  } catch (const std::exception&) {
+    return KGS_E_ARG;
+  }
+}
+
 int kgs_verify_ptau(int kind, const char* ptau_path, int nbits, int npols, int selected, const uint8_t* commitments,
                     const uint8_t* evaluations) {
   uint8_t t2[128];

@@ -303,6 +303,7 @@ struct Job {
                // 7 = one proof of several arguments (proveMulti)
                // 8 = the G1 transform (g1Ntt), 9 = a commitment from evaluations (commitEvals)
                // 10 = every opening of a polynomial on its domain (kzgOpenAll)
+               // 11 = every coset opening of a polynomial (kzgOpenCosets)
   int rc = 0;
   std::string err;
   // load
@@ -324,7 +325,8 @@ struct Job {
   std::vector<kgs_ctx_t*> ranks;
   // msmPoints: bases and standard-form scalars (copied: the call returns before the work runs);
   // g1Ntt: the points in `bases`, transformed in place; commitEvals: the evaluations in `scal`;
-  // kzgOpenAll: the coefficients in `scal`, the proofs in `bases`, the evaluations in `ev`
+  // kzgOpenAll / kzgOpenCosets: the coefficients in `scal`, the proofs in `bases`, the evaluations in `ev`
+  // (ntt_logm = nbits, ntt_inverse = lbits)
   std::vector<uint8_t> bases, scal;
   uint8_t msm_out[64];
   int ntt_logm = 0, ntt_inverse = 0;
@@ -518,6 +520,11 @@ static void job_execute(napi_env, void* data) {
     j->bases.resize((size_t)64 << j->ntt_logm);
     j->ev.resize((size_t)32 << j->ntt_logm);
     j->rc = kgs_kzg_open_all(j->ctx, j->scal.data(), j->scal.size() / 32, j->ntt_logm, j->bases.data(), j->ev.data());
+  } else if (j->op == 11) {
+    j->bases.resize((size_t)64 << (j->ntt_logm - j->ntt_inverse));
+    j->ev.resize((size_t)32 << j->ntt_logm);
+    j->rc = kgs_kzg_open_cosets(j->ctx, j->scal.data(), j->scal.size() / 32, j->ntt_logm, j->ntt_inverse, j->bases.data(),
+                                j->ev.data());
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -550,7 +557,7 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->msm_out, 64));
   } else if (j->op == 8) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->bases.data(), j->bases.size()));
-  } else if (j->op == 10) {
+  } else if (j->op == 10 || j->op == 11) {
     napi_value o;
     napi_create_object(env, &o);
     napi_set_named_property(env, o, "proofs", make_u8(env, j->bases.data(), j->bases.size()));
@@ -1142,6 +1149,59 @@ static napi_value KzgOpenAll(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_kzg_open_all");
 }
 
+// kzgOpenCosets(ctx, coefMont, nBits, lBits) -> Promise<{proofs, evals}> over the SRS resident on ctx
+// (kgs_kzg_open_cosets): one proof per coset of 2^lBits points of the domain of 2^nBits, 2^(nBits - lBits) x
+// 64 B affine LEM, and the polynomial's values on the domain, 2^nBits x 32 B Montgomery
+static napi_value KzgOpenCosets(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  int32_t nbits = -1, lbits = -1;
+  Job* j = new Job();
+  j->op = 11;
+  j->ctx = get_ctx(env, argv[0]);
+  j->scal = bytes_of(env, argv[1]);
+  napi_get_value_int32(env, argv[2], &nbits);
+  napi_get_value_int32(env, argv[3], &lbits);
+  if (j->scal.size() % 32 || nbits < 0 || nbits > 23 || lbits < 0 || lbits > nbits ||
+      j->scal.size() / 32 > ((size_t)1 << nbits)) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgOpenCosets: expected at most 2^nBits Montgomery coefficients of 32 B, nBits <= 23, lBits <= nBits");
+    return nullptr;
+  }
+  j->ntt_logm = nbits;
+  j->ntt_inverse = lbits;
+  return queue(env, j, "kgs_kzg_open_cosets");
+}
+
+// kzgVerifyCoset(commit, nBits, lBits, index, ysMont, proof, srsG1, tauLG2) -> bool (kgs_kzg_verify_coset, host
+// only): the check of one coset opening; srsG1 = the first 2^lBits points [tau^k]_1, tauLG2 = [tau^l]_2
+static napi_value KzgVerifyCoset(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  int32_t nbits = -1, lbits = -1;
+  int64_t index = -1;
+  std::vector<uint8_t> cm = bytes_of(env, argv[0]), ys = bytes_of(env, argv[4]), pf = bytes_of(env, argv[5]),
+                       srs = bytes_of(env, argv[6]), t2 = bytes_of(env, argv[7]);
+  napi_get_value_int32(env, argv[1], &nbits);
+  napi_get_value_int32(env, argv[2], &lbits);
+  napi_get_value_int64(env, argv[3], &index);
+  if (nbits < 0 || nbits > 28 || lbits < 0 || lbits > nbits || index < 0 || cm.size() != 64 || pf.size() != 64 ||
+      t2.size() != 128 || ys.size() != ((size_t)32 << lbits) || srs.size() < ((size_t)64 << lbits)) {
+    napi_throw_error(env, nullptr, "kzgVerifyCoset: expected 64 B commit and proof, 2^lBits x 32 B values, at least 2^lBits x 64 B SRS points, 128 B [tau^l]_2");
+    return nullptr;
+  }
+  const int rc = kgs_kzg_verify_coset(cm.data(), nbits, lbits, (uint64_t)index, ys.data(), pf.data(), srs.data(), t2.data());
+  if (rc < 0) {
+    napi_throw_error(env, nullptr, "kzgVerifyCoset: index out of range or [tau^l]_2 not on its curve");
+    return nullptr;
+  }
+  napi_value out;
+  napi_get_boolean(env, rc == 1, &out);
+  return out;
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1178,6 +1238,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"g1Ntt", nullptr, G1Ntt, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitEvals", nullptr, CommitEvals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgOpenAll", nullptr, KzgOpenAll, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgOpenCosets", nullptr, KzgOpenCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgVerifyCoset", nullptr, KzgVerifyCoset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

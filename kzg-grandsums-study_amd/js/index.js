@@ -20,6 +20,11 @@ module.exports = {
     // coefficients) at every point of its domain at once (kgs_kzg_open_all); one of them is checked with
     // curve.pairingEq(proof, [tau]_2, -(C - y G + z proof), [1]_2)
     kzg_open_all: require("./src/backend").kzgOpenAll,
+    // kzg_open_cosets(pTauFilename, coefs, lBits) -> {proofs, evals}: one proof per coset of 2^lBits points of
+    // the domain (kgs_kzg_open_cosets); kzg_verify_coset(commit, nBits, lBits, index, ysMont, proof, srsG1,
+    // tauLG2) -> bool checks one of them on the host (kgs_kzg_verify_coset)
+    kzg_open_cosets: require("./src/backend").kzgOpenCosets,
+    kzg_verify_coset: require("./src/backend").kzgVerifyCoset,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

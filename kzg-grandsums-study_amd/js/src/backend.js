@@ -231,6 +231,33 @@ async function kzgOpenAll(pTauFilename, coefs) {
     });
 }
 
+// Every coset opening of the polynomial with the Montgomery coefficients `coefs` (a Uint8Array or a BigBuffer
+// of 32-byte elements): the domain is the smallest 2^k that holds them (and at least 2^lBits points), a coset
+// has 2^lBits points, over the SRS of pTauFilename (kgs_kzg_open_cosets; the SRS side is cached on the device)
+// -> Promise<{proofs: 2^(k - lBits) x 64 B affine LEM, evals: 2^k x 32 B Montgomery}>; proof i covers the
+// values evals[i + 2^(k - lBits) j], j < 2^lBits
+async function kzgOpenCosets(pTauFilename, coefs, lBits) {
+    const key = path.resolve(pTauFilename);
+    const c = contiguous(coefs);
+    const n = c.byteLength / 32;
+    if (!Number.isInteger(n) || n > (1 << 23) || !Number.isInteger(lBits) || lBits < 0 || lBits > 23) {
+        throw new Error("kzg_open_cosets: the coefficients must be at most 2^23 32-byte elements, lBits in 0 .. 23");
+    }
+    const nBits = Math.max(n > 1 ? Math.ceil(Math.log2(n)) : 0, lBits);
+    return withContext(async slot => {
+        await ensureSrs(slot, key, nBits);
+        return load().kzgOpenCosets(slot.ctx, c, nBits, lBits);
+    });
+}
+
+// The check of one coset opening on the host (kgs_kzg_verify_coset) -> bool. commit / proof: 64 B affine LEM;
+// ysMont: the coset's 2^lBits values, 32 B Montgomery each; srsG1: the first 2^lBits points [tau^k]_1, 64 B
+// affine LEM each; tauLG2: [tau^(2^lBits)]_2, 128 B LEM
+function kzgVerifyCoset(commit, nBits, lBits, index, ysMont, proof, srsG1, tauLG2) {
+    return load().kzgVerifyCoset(contiguous(commit), nBits, lBits, index, contiguous(ysMont), contiguous(proof),
+        contiguous(srsG1), contiguous(tauLG2));
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -283,4 +310,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
