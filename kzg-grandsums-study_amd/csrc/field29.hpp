@@ -12,8 +12,9 @@
 // Values are Montgomery residues with R = 2^261 (x is held as x * 2^261 mod q, NOT reduced below
 // q). The bound analysis of every operation in g1_acc29::add_aff below (value bound and limb bound
 // of each intermediate, column overflow of each product) is reproduced by DESIGN.md §MSM and was
-// re-derived by tests/test_field29.py (interval arithmetic over the exact constants); accumulator
-// coordinates stay < 2^258.6.
+// re-derived by tests/test_field29.py (interval arithmetic over the exact constants) and, with the
+// rows that reduce by Q* (reduce_row_qstar), by tests/test_field29_qstar.py; accumulator coordinates
+// stay < 2^258.6 (fixed point 2^258.15 with either row set).
 // Conversions: the MSM table stores affine coordinates as x * 2^261 mod q (canonical, packed into
 // 8 x 32-bit words like every other field element); bucket sums leave through mul(., 2^256 mod q),
 // which yields the usual 256-bit Montgomery form (< 2q, one conditional subtraction).
@@ -30,6 +31,21 @@
 #define KGS_M32_ROWS_MUL2 8
 #endif
 static_assert(KGS_M32_ROWS <= 8 && KGS_M32_ROWS_MUL2 <= 8, "column bounds of fq29::reduce_row32");
+// Leading CIOS rows that reduce by Q* = k*q = -1 mod 2^32 (fq29::reduce_row_qstar: no multiply for m),
+// per product kind: mul/sqr, the products whose columns carry_sub reads, and mul2. At most 7 (the
+// value and column bounds are re-derived by tests/test_field29_qstar.py); 0 builds the parent's rows
+// for A/B. The rows after them take the 32-bit m (KGS_M32_ROWS*) or the 29-bit m as before.
+#ifndef KGS_QSTAR_ROWS
+#define KGS_QSTAR_ROWS 7
+#endif
+#ifndef KGS_QSTAR_ROWS_CSUB
+#define KGS_QSTAR_ROWS_CSUB 7
+#endif
+#ifndef KGS_QSTAR_ROWS_MUL2
+#define KGS_QSTAR_ROWS_MUL2 7
+#endif
+static_assert(KGS_QSTAR_ROWS <= 7 && KGS_QSTAR_ROWS_CSUB <= 7 && KGS_QSTAR_ROWS_MUL2 <= 7,
+              "value and column bounds of fq29::reduce_row_qstar");
 
 namespace kgs {
 namespace f29 {
@@ -42,6 +58,12 @@ struct L9 {
 };
 constexpr L9 Q = {{0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u, 0x02db40c0u, 0x00a6e141u,
                    0x0e5c2634u, 0x0030644eu}};
+// Q* = QSTAR_K * q = (2^32 - 1) + 2^29 * r with QSTAR_K = -q^-1 mod 2^32 (the smallest multiple of q
+// that is -1 mod 2^32; r is a multiple of 8 below 2^257). QSTAR_R holds r's nine 29-bit limbs with 8
+// added to limb 0: the 8*m of reduce_row_qstar's column-0 carry rides on the m * r_0 product.
+constexpr uint32_t QSTAR_K = 0xe4866389u;
+constexpr L9 QSTAR_R = {{0x02e38790u, 0x0d1e68dcu, 0x148e556bu, 0x10c54699u, 0x0f93f7a8u, 0x02d6db27u, 0x05f64f9au,
+                         0x1010b67bu, 0x015995e9u}};
 constexpr L9 ONE = {{0x157ccc21u, 0x141c2758u, 0x185230d3u, 0x014c0419u, 0x0aa36fb9u, 0x1d4240ceu, 0x11d54c07u,
                      0x052ac7a8u, 0x000dc836u}};  // 2^261 mod q
 constexpr L9 C256 = {{0x058f0d9du, 0x1aea1c6eu, 0x11c2cf74u, 0x11d651ebu, 0x1462c0a7u, 0x11b7bc3cu, 0x1cbd99bau,
@@ -162,9 +184,9 @@ struct fq29 {
   // and the mask: 3 instead of 5 VALU per row. m < 2^32 adds < 2^(29 i + 32) q to the reduced value in
   // row i, so rows 0..7 take it (together < 2^-25 q over the 2^261 of the division) and row 8 keeps
   // the 29-bit m (the result stays < a*b/2^261 + q(1 + 2^-25)). Columns: mul/sqr of normalised
-  // operands < 2^63.0 (outputs < 2^62.6, read as int64 by carry_sub); mul2 with add_aff's / add's
-  // operand limb bounds < 2^64 — tests/test_field29.py re-derives every column bound row by row and
-  // runs the exact row schedule on Python integers.
+  // operands < 2^63.0 (outputs < 2^62.6) with these rows alone (KGS_QSTAR_ROWS* = 0); mul2 with
+  // add_aff's / add's operand limb bounds < 2^64 — tests/test_field29.py re-derives every column
+  // bound row by row and runs the exact row schedule on Python integers.
   __device__ __forceinline__ static void reduce_row32(uint64_t (&t)[9], uint32_t eight) {
     const uint32_t m = (uint32_t)t[0] * f29::INV32;
     const uint64_t u = (uint64_t)m * f29::Q.v[0] + t[0];
@@ -175,20 +197,40 @@ struct fq29 {
     t[0] = (uint64_t)(uint32_t)(u >> 32) * eight + t[0];
     t[8] = 0;
   }
+  // The step with the modulus multiple Q* = -1 mod 2^32 (f29::QSTAR_R): m is t0's low word itself, no
+  // multiply. t0 + m*(2^32 - 1) = (hi32(t0) + m) * 2^32, so column 0 vanishes and its carry into
+  // column 1 is 8*hi32(t0) + 8*m; the rest of m*Q* is m * r_j onto columns 1..9 (column 9 is the next
+  // row's top column, 0 until now). Nine mads m * QSTAR_R[j] (limb 0 carries the 8*m) and the carry
+  // mad: 10 VOP3 per row against reduce_row32's 11. Row i adds < 2^(32 + 29 i) Q* / 2^261 to the
+  // result, Q* < 2^286: rows 0..6 together < 2^-23 q, so at most 7 rows take it. r's limbs are larger
+  // than q's, so the columns rise: mul/sqr of normalised operands < 2^63.07 (outputs < 2^63.06:
+  // carry_sub reads them unsigned), mul2 < 2^63.97 — tests/test_field29_qstar.py
+  // re-derives every bound with the header's row counts and runs the exact schedule on Python integers.
+  __device__ __forceinline__ static void reduce_row_qstar(uint64_t (&t)[9], uint32_t eight) {
+    const uint32_t m = (uint32_t)t[0], h = (uint32_t)(t[0] >> 32);
+#pragma unroll
+    for (int j = 0; j < 8; j++) t[j] = (uint64_t)m * f29::QSTAR_R.v[j] + t[j + 1];
+    t[8] = (uint64_t)m * f29::QSTAR_R.v[8];
+    t[0] = (uint64_t)h * eight + t[0];
+  }
   // 8 as an opaque SGPR value (keeps reduce_row32's carry a v_mad_u64_u32)
   __device__ __forceinline__ static uint32_t opaque8() {
     uint32_t e = 8;
     asm volatile("" : "+s"(e));
     return e;
   }
-  template <int M32_ROWS>
+  template <int QSTAR_ROWS, int M32_ROWS>
   __device__ __forceinline__ static void reduce_row_at(uint64_t (&t)[9], int i, uint32_t eight) {
-    if (i < M32_ROWS) reduce_row32(t, eight); else reduce_row(t);
+    if (i < QSTAR_ROWS) reduce_row_qstar(t, eight);
+    else if (i < M32_ROWS) reduce_row32(t, eight);
+    else reduce_row(t);
   }
 
   // Montgomery product a*b*2^-261 (CIOS, 64-bit column accumulators, no carry words).
-  // Needs 9*max(a_j)*max(b_j) + 2^32 * sum(q_j) + 2^36 < 2^64 (a_j, b_j < 2^29; reduce_row32 in
-  // rows 0..7) and a*b < 2^261 * (2^261 - q); the result is < a*b/2^261 + q(1 + 2^-25).
+  // Needs 9*max(a_j)*max(b_j) + 2^32 * sum(QSTAR_R_j) + 2^36 < 2^64 (a_j, b_j < 2^29; QSTAR_ROWS rows
+  // of reduce_row_qstar, then reduce_row32 up to row 7) and a*b < 2^261 * (2^261 - q); the result is
+  // < a*b/2^261 + q(1 + 2^-22). QSTAR_ROWS defaults to the count for products that feed carry_sub.
+  template <int QSTAR_ROWS = KGS_QSTAR_ROWS_CSUB>
   __device__ __forceinline__ static cols mul_cols(const fq29& a, const fq29& b) {
     const uint32_t eight = opaque8();
     cols r;
@@ -198,7 +240,7 @@ struct fq29 {
     for (int i = 0; i < 9; i++) {
 #pragma unroll
       for (int j = 0; j < 9; j++) r.t[j] = (uint64_t)a.l[i] * b.l[j] + r.t[j];
-      reduce_row_at<KGS_M32_ROWS>(r.t, i, eight);
+      reduce_row_at<QSTAR_ROWS, KGS_M32_ROWS>(r.t, i, eight);
     }
     return r;
   }
@@ -207,6 +249,7 @@ struct fq29 {
   // once (2a_i * a_j, j > i, and a_i^2 on the diagonal): 45 + 81 mads instead of 162. Row i adds to
   // absolute columns 2i..i+8, which sit at t[i..8] after i shifts. A column receives at most 5
   // products (<= 2 * max(a_j)^2 each), so it stays below mul's bound for a normalised a.
+  template <int QSTAR_ROWS = KGS_QSTAR_ROWS_CSUB>
   __device__ __forceinline__ static cols sqr_cols(const fq29& a) {
     const uint32_t eight = opaque8();
     uint32_t d[9];
@@ -220,7 +263,7 @@ struct fq29 {
       r.t[i] = (uint64_t)a.l[i] * a.l[i] + r.t[i];
 #pragma unroll
       for (int j = i + 1; j < 9; j++) r.t[j] = (uint64_t)d[i] * a.l[j] + r.t[j];
-      reduce_row_at<KGS_M32_ROWS>(r.t, i, eight);
+      reduce_row_at<QSTAR_ROWS, KGS_M32_ROWS>(r.t, i, eight);
     }
     return r;
   }
@@ -228,7 +271,8 @@ struct fq29 {
   // (a*b + c*d)*2^-261 with ONE Montgomery reduction (lazy reduction of a sum of products): each CIOS
   // row adds both rows of partial products before its reduction step, 243 mads instead of 324.
   // Needs 9*(max a_j * max b_j + max c_j * max d_j) + 9*(2^29)^2 + 2^36 < 2^64 (a and c normalised)
-  // and a*b + c*d < 2^261 * (2^261 - q); the result is < (a*b + c*d)/2^261 + q.
+  // and a*b + c*d < 2^261 * (2^261 - q); the result is < (a*b + c*d)/2^261 + q(1 + 2^-22). With
+  // KGS_QSTAR_ROWS_MUL2 = 7 and add_aff's / add's operand limb bounds the columns reach 2^63.97.
   __device__ __forceinline__ static cols mul2_cols(const fq29& a, const fq29& b, const fq29& c2, const fq29& d2) {
     const uint32_t eight = opaque8();
     cols r;
@@ -240,7 +284,7 @@ struct fq29 {
       for (int j = 0; j < 9; j++) r.t[j] = (uint64_t)a.l[i] * b.l[j] + r.t[j];
 #pragma unroll
       for (int j = 0; j < 9; j++) r.t[j] = (uint64_t)c2.l[i] * d2.l[j] + r.t[j];
-      reduce_row_at<KGS_M32_ROWS_MUL2>(r.t, i, eight);
+      reduce_row_at<KGS_QSTAR_ROWS_MUL2, KGS_M32_ROWS_MUL2>(r.t, i, eight);
     }
     return r;
   }
@@ -257,24 +301,26 @@ struct fq29 {
     }
     return r;
   }
-  // norm(x + K - b) in ONE carry pass (K = spread(k, s): every limb of K >= b's limb; x's columns
-  // < 2^63, read as int64)
+  // norm(x + K - b) in ONE carry pass (K = spread(k, s): every limb of K >= b's limb, so every term
+  // is nonnegative and the pass runs unsigned; x's columns < 2^63.1, the sums < 2^64)
   template <uint32_t K, uint32_t S>
   __device__ __forceinline__ static fq29 carry_sub(const cols& x, const fq29& b) {
     constexpr f29::L9 Kc = f29::spread(K, S);
     fq29 r;
-    int64_t c = 0;
+    uint64_t c = 0;
 #pragma unroll
     for (int j = 0; j < 9; j++) {
-      const int64_t s = (int64_t)(Kc.v[j] - b.l[j]) + (int64_t)x.t[j] + c;
+      const uint64_t s = (uint64_t)(Kc.v[j] - b.l[j]) + x.t[j] + c;
       r.l[j] = j < 8 ? ((uint32_t)s & f29::MASK) : (uint32_t)s;
       c = s >> 29;
     }
     return r;
   }
 
-  __device__ __forceinline__ static fq29 mul(const fq29& a, const fq29& b) { return carry(mul_cols(a, b)); }
-  __device__ __forceinline__ static fq29 sqr(const fq29& a) { return carry(sqr_cols(a)); }
+  __device__ __forceinline__ static fq29 mul(const fq29& a, const fq29& b) {
+    return carry(mul_cols<KGS_QSTAR_ROWS>(a, b));
+  }
+  __device__ __forceinline__ static fq29 sqr(const fq29& a) { return carry(sqr_cols<KGS_QSTAR_ROWS>(a)); }
   __device__ __forceinline__ static fq29 mul2(const fq29& a, const fq29& b, const fq29& c2, const fq29& d2) {
     return carry(mul2_cols(a, b, c2, d2));
   }
@@ -307,9 +353,21 @@ struct g1_acc29 {
   // this += (x, +-y): x, y = table coordinates (x*2^261 mod q, canonical, packed words);
   // madd-2008-s with the same special cases as g1_xyzz::add_aff. ZP = false: the caller knows that
   // (x, y) is never the zero point (a table built from an SRS without one), and the test of its 16
-  // words is compiled out.
+  // words is compiled out. reload(rx, ry) hands the point's 16 words to the doubling branch a second
+  // time: a caller that can fetch them again (k_accumulate: from the table) keeps them out of the
+  // registers that stay live across the common path for the lanes waiting to take the rare one.
   template <bool ZP = true>
   __device__ __forceinline__ void add_aff(const uint32_t* xw, const uint32_t* yw, bool negy) {
+    add_aff<ZP>(xw, yw, negy, [&](uint32_t* rx, uint32_t* ry) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        rx[i] = xw[i];
+        ry[i] = yw[i];
+      }
+    });
+  }
+  template <bool ZP, class Reload>
+  __device__ __forceinline__ void add_aff(const uint32_t* xw, const uint32_t* yw, bool negy, Reload reload) {
     if (ZP) {
       uint32_t z = 0;
 #pragma unroll
@@ -339,9 +397,11 @@ struct g1_acc29 {
     if (PP.maybe_zero8()) {  // rare: decide exactly
       if (P.to_fq().is_zero()) {
         if (R.to_fq().is_zero()) {  // same point: doubling (256-bit path, converted back)
+          uint32_t rx[8], ry[8];
+          reload(rx, ry);
           g1_aff a;
-          a.x = x2.to_fq();
-          a.y = y2.to_fq();
+          a.x = fq29::unpack(rx).to_fq();
+          a.y = fq29::unpack(ry).to_fq();
           if (negy) a.y = a.y.neg();
           const g1_xyzz d = g1_xyzz::dbl_aff(a);
           X = fq29::from_fq(d.X);

@@ -10,13 +10,23 @@
 // and far more instruction-level parallelism for the NTT passes, which run at 2-3 waves per SIMD.
 // The twiddle w comes pre-converted from the domain tables (ntt.hip k_tw29): w * 2^261 mod p,
 // canonical, as 9 limbs in a 10-word record, so the product a * w * 2^261 * 2^-261 lands in the same
-// Montgomery domain (R = 2^256) as a. Same reduction scheme as field29.hpp's fq29 (32-bit m in CIOS
-// rows 0..7, one carry mad per row, 29-bit m in row 8); BN254's r is 1 + 2^28 mod 2^29, so
-// -r^-1 mod 2^32 on the low limb is 2^28 - 1. Bounds (tests/test_fr29.py re-derives them and runs the
-// exact row schedule on Python integers): for a < 2^256 (unpacked limbs < 2^29, top limb < 2^24) and
-// w < p, every column stays < 2^63.14 (the m * P[j] terms dominate) and the result is < a*w/2^261 + p(1 + 2^-25) < 2p.
+// Montgomery domain (R = 2^256) as a. Same reduction scheme as field29.hpp's fq29: rows 0..6 reduce by
+// R* = k*r = -1 mod 2^32 (m is the column's low word, no multiply; r29::QSTAR_R), row 7 takes the
+// 32-bit m = -t0/P[0] mod 2^32 (BN254's r is 1 + 2^28 mod 2^29, so -P[0]^-1 mod 2^32 is 2^28 - 1),
+// row 8 the 29-bit m; one carry mad per row. Bounds (tests/test_fr29_qstar.py re-derives them and runs
+// the exact row schedule on Python integers; tests/test_fr29.py does so for the rows without R*,
+// KGS_QSTAR_ROWS_FR = 0: columns < 2^63.14): for a < 2^256 (unpacked limbs < 2^29, top limb < 2^24) and
+// w < p, every column stays < 2^63.63 (the m * QSTAR_R[j] terms dominate) and the result is
+// < a*w/2^261 + p(1 + 2^-22) < 1.04 p < 2p.
 #pragma once
 #include "field.hpp"
+
+// Leading CIOS rows of mul29 that reduce by R* = k*r = -1 mod 2^32 (no multiply for m, see below); at
+// most 7 (bounds: tests/test_fr29_qstar.py); 0 builds the parent's rows for A/B
+#ifndef KGS_QSTAR_ROWS_FR
+#define KGS_QSTAR_ROWS_FR 7
+#endif
+static_assert(KGS_QSTAR_ROWS_FR <= 7, "value and column bounds of mul29's R* rows");
 
 namespace kgs {
 namespace r29 {
@@ -25,6 +35,16 @@ constexpr uint32_t P[9] = {0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0
                            0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};  // r, 29-bit limbs
 constexpr uint32_t INV = 0x0fffffffu;    // -r^-1 mod 2^29
 constexpr uint32_t INV32 = 0x0fffffffu;  // -P[0]^-1 mod 2^32
+// R* = QSTAR_K * r = (2^32 - 1) + 2^29 * s with QSTAR_K = -r^-1 mod 2^32 (s a multiple of 8 below
+// 2^257). QSTAR_R holds s's nine 29-bit limbs with 8 added to limb 0. A row that reduces by R* takes
+// m = t0's low word as it is: t0 + m (2^32 - 1) = (hi32(t0) + m) 2^32, so column 0 vanishes, its carry
+// into column 1 is 8 hi32(t0) + 8 m (the 8 m rides on m * QSTAR_R[0]), and m * s lands on columns
+// 1..9: nine mads and the carry mad, 10 VOP3 against the 11 of a 32-bit-m row (same scheme as
+// field29.hpp's fq29::reduce_row_qstar). Row i adds < 2^(32 + 29 i) R* / 2^261 to the result: rows
+// 0..6 together < 2^-23 r.
+constexpr uint32_t QSTAR_K = 0xefffffffu;
+constexpr uint32_t QSTAR_R[9] = {0x08f05368u, 0x1a996a5bu, 0x13e27f6bu, 0x15166c9eu, 0x1e906a17u,
+                                 0x04c58463u, 0x16877334u, 0x0b82ba37u, 0x016af04cu};
 constexpr int W29_WORDS = 10;            // twiddle record: 9 limbs + 1 pad (kernels.hpp TW29_WORDS)
 // 32 * 2^256 mod r in 8 x 32-bit words (Montgomery form of 32): x * C32 turns x * 2^256 into x * 2^261
 constexpr uint32_t C32[8] = {0x8fffff57u, 0x2fd4e156u, 0xa494b01au, 0x75bba827u,
@@ -74,7 +94,13 @@ __device__ __forceinline__ fr mul29(const fr& A, const W29& w) {
   for (int i = 0; i < 9; i++) {
 #pragma unroll
     for (int j = 0; j < 9; j++) t[j] = (uint64_t)a[i] * w.l[j] + t[j];
-    if (i < 8) {  // 32-bit m: t0 + m P0 has 32 zero low bits, its carry is 8 x its high word
+    if (i < KGS_QSTAR_ROWS_FR) {  // reduce by R*: m = lo32(t0), no multiply
+      const uint32_t m = (uint32_t)t[0], h = (uint32_t)(t[0] >> 32);
+#pragma unroll
+      for (int j = 0; j < 8; j++) t[j] = (uint64_t)m * r29::QSTAR_R[j] + t[j + 1];
+      t[8] = (uint64_t)m * r29::QSTAR_R[8];
+      t[0] = (uint64_t)h * eight + t[0];
+    } else if (i < 8) {  // 32-bit m: t0 + m P0 has 32 zero low bits, its carry is 8 x its high word
       const uint32_t m = (uint32_t)t[0] * r29::INV32;
       const uint64_t u = (uint64_t)m * p0 + t[0];
 #pragma unroll

@@ -799,7 +799,16 @@ __global__ void __launch_bounds__(256, VW) k_accumulate(uint32_t* __restrict__ s
     bnext = offsets[b + 2 <= nbins ? b + 2 : nbins];
     const uint32_t xw[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
     const uint32_t yw[8] = {a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
-    acc.add_aff<ZP>(xw, yw, (v & 0x80000000u) != 0);
+    // the doubling branch (two equal points in a bucket) reads its point again from the table,
+    // through a pointer the compiler cannot match with the gather above: the 16 words then die with
+    // the first two products instead of staying live across the whole add for that branch
+    acc.add_aff<ZP>(xw, yw, (v & 0x80000000u) != 0, [&](uint32_t* rx, uint32_t* ry) {
+      const uint4* pr = reinterpret_cast<const uint4*>(table + 16 * (uint64_t)(v & KGS_DIAG_GATHER_MASK));
+      asm volatile("" : "+v"(pr));
+      const uint4 r0 = pr[0], r1 = pr[1], r2 = pr[2], r3 = pr[3];
+      rx[0] = r0.x; rx[1] = r0.y; rx[2] = r0.z; rx[3] = r0.w; rx[4] = r1.x; rx[5] = r1.y; rx[6] = r1.z; rx[7] = r1.w;
+      ry[0] = r2.x; ry[1] = r2.y; ry[2] = r2.z; ry[3] = r2.w; ry[4] = r3.x; ry[5] = r3.y; ry[6] = r3.z; ry[7] = r3.w;
+    });
     a0 = n0; a1 = n1; a2 = n2; a3 = n3;
     v = vn;
     vn = vnn;

@@ -17,12 +17,14 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kzg-grandsums-study_amd", "csrc")
-SYM = "_ZN3kgs12k_accumulateILi3EEEvPjS1_S1_PKjS3_jS3_jS1_j"
+SYM = "_ZN3kgs12k_accumulateILi3ELb0EEEvPjS1_S1_PKjS3_jS3_jS1_jj"  # k_accumulate<3, false>: the headline's build
 
 
 def compile_asm(src_dir, out):
+    # ISA_MIX_FLAGS: extra compiler flags, e.g. field29.hpp's row knobs (-DKGS_QSTAR_ROWS=0 ...)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only",
-                           "-S", os.path.join(src_dir, "msm.hip"), "-o", out], stderr=subprocess.DEVNULL)
+                           "-S", os.path.join(src_dir, "msm.hip"), "-o", out] + os.environ.get("ISA_MIX_FLAGS", "").split(),
+                          stderr=subprocess.DEVNULL)
 
 
 def blocks_of(asm):

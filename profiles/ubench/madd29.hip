@@ -1,5 +1,7 @@
 // Microbenchmark: XYZZ mixed-add throughput, fq29 accumulator vs the 8x32-bit lazy accumulator
 // (register-resident operands, no memory traffic).
+// Row knobs of field29.hpp for A/B (UBENCH_FLAGS of run.sh): -DKGS_QSTAR_ROWS=N -DKGS_QSTAR_ROWS_CSUB=N
+// -DKGS_QSTAR_ROWS_MUL2=N, N = 0..7 leading CIOS rows that reduce by Q* (0: the 32-bit-m rows only).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -50,6 +52,8 @@ int main() {
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
+  printf("Q* rows: mul/sqr %d, carry_sub producers %d, mul2 %d\n", KGS_QSTAR_ROWS, KGS_QSTAR_ROWS_CSUB,
+         KGS_QSTAR_ROWS_MUL2);
   for (int v = 0; v < 2; v++) {
     float ms = 0;
     for (int rep = 0; rep < 3; rep++) {
