@@ -716,6 +716,96 @@ int kgs_kzg_open_cosets_cached(kgs_ctx_t* ctx, int nbits, int lbits);
  * a range error or a tau_l_g2 off its curve. */
 int kgs_kzg_verify_coset(const uint8_t commit_lem[64], int nbits, int lbits, uint64_t index, const uint8_t* ys_mont,
                          const uint8_t proof_lem[64], const uint8_t* srs_g1_lem, const uint8_t tau_l_g2[128]);
+
+/* ---- batch verifier for coset openings: many (commitment, coset, values, proof) tuples against one SRS, one
+ * pairing check. Notation as for kgs_kzg_open_cosets: n = 2^nbits, l = 2^lbits, m = n / l,
+ * w = Fr.w[nbits], a_i = w^(i l). Opening k < count is (commitment c(k) = commit_of[k], coset i_k = index[k], the
+ * l values y_k = ys_mont[k l .. k l + l), proof pi_k). Every opening's equation is linear in G1, so under weights
+ * w_k = rho^k the batch is accepted iff
+ *   e(-A, [tau^l]_2) * e(B, [1]_2) == 1
+ *   A = sum_k w_k pi_k
+ *   B = sum_k w_k C_c(k) + sum_k (w_k a_{i_k}) pi_k - [D(tau)]_1
+ *   D = sum_k w_k I_k, that is D_j = sum_k w_k w^(-i_k j) J_{k,j} for j < l, J_k the inverse transform of size l of
+ *       y_k in kgs_ntt's convention: the interpolant kgs_kzg_verify_coset builds (kgs_coset_interp_fold below)
+ * With count == 1 (rho^0 = 1) this is kgs_kzg_verify_coset's equation, and the verdict is the same.
+ *
+ * Weights (deterministic; LE32 / LE64 = 4 / 8 bytes little-endian)
+ *   seed = seed32 if it is given, else keccak256("kgs-verify-cosets-batch-v1" || tau_l_g2 (128 B) || LE32(nbits) ||
+ *          LE32(lbits) || LE64(ncommits) || commits || LE64(count) || commit_of (LE32 each) || index (LE64 each) ||
+ *          ys || proofs)
+ *   rho  = keccak256("kgs-verify-cosets-batch-v1/rho" || seed) read as a little-endian integer mod r; 0 -> 1
+ *   w_k  = rho^k
+ * A caller's seed32 saves hashing count * l * 32 bytes on one host thread; it MUST be unpredictable to whoever
+ * made the proofs (fresh randomness drawn after the batch is fixed, or a hash that covers all of it).
+ * Soundness: the pairing residues of the openings are fixed before rho is (the seed hashes everything the check
+ * depends on, or is drawn afterwards). If some opening fails its own equation, the batch equation is a nonzero
+ * polynomial of degree < count in rho, so in the random-oracle model a batch holding an invalid opening passes
+ * the aggregate check with probability at most count / r < 2^-227 for count <= 2^26.
+ *
+ * Structural checks, as in the single check: an opening whose proof or commitment is no canonical point of the
+ * curve, with a value >= r, an index >= m or a commit_of >= ncommits is marked invalid before the aggregate
+ * check and enters it with weight 0. An SRS point off the curve makes every opening invalid (returns 0).
+ *
+ * Returns 1 if every opening is valid, 0 if some opening is invalid, a negative KGS_E_* for an error. With
+ * valid_out == NULL only that verdict is computed. With valid_out (count bytes, 1 valid / 0 invalid) a failing
+ * batch is bisected over contiguous index ranges: under a failing parent the left half is checked; if it passes
+ * the right half is known to fail and is not checked. With b invalid openings that is at most
+ * 1 + 2 b ceil(log2 count) checks. A sub-range is folded again, with the same weights; on the GPU path the inputs
+ * stay on the device between the checks.
+ *   nbits, lbits  with a context nbits 0 .. 23 (what the shared domain tables cover), on the host 0 .. 28;
+ *                 lbits 0 .. nbits; with a context count * l <= 2^26. On the GPU the fold covers lbits <= 10:
+ *                 a batch of larger cosets folds on the host (the _device twin answers KGS_E_ARG)
+ *   commits_lem   ncommits affine LEM commitments (64 B); one commitment may serve many openings
+ *   commit_of     count indices into commits_lem;   index  count coset indices
+ *   ys_mont       count * l values, 32 B Montgomery, the rows contiguous;   proofs_lem  count x 64 B affine LEM
+ *   srs_g1_lem    the first l points [tau^k]_1 (affine LEM);   tau_l_g2  [tau^l]_2 (kgs_ptau_read_tau_g2_pow)
+ *   seed32        NULL, or 32 bytes (see above)
+ * KGS_E_ARG: a NULL buffer with work to do, nbits / lbits / count out of range, a tau_l_g2 off its curve, a
+ * context attached to a rank group or with MSM sharding on. count == 0 returns 1 and touches nothing.
+ * ctx == NULL computes everything on the host (no GPU is touched). With a context a batch of fewer than 24 terms
+ * (3 count + l; the measured crossover) folds on the host as well, and diag->on_gpu tells which
+ * path ran; the environment variable KGS_VERIFY_COSETS_FOLD = "gpu" | "host" forces either. On the GPU path the
+ * on-curve checks (k_g1_on_curve), the range checks (inside the interpolation kernel), the weights, D and the
+ * terms of A and B are computed on the device, and A and B are summed there by kgs_msm_points' buckets
+ * (KGS_VERIFY_COSETS_MSM = "fold" runs kgs_g1_lincomb's fold instead: slower at every size, kept for the A/B);
+ * the host does the hash, the pairing checks and the bisection. Context contract as for kgs_g1_mul_sum and kgs_kzg_open_cosets: device
+ * buffers of the call's own; the window tables, the Lagrange cache, the fk rows and the prover's work buffers
+ * are untouched; the domain tables may grow to 2^nbits; the context is idle on return, on error paths too. */
+typedef struct {            /* optional; every pointer member optional (NULL: not wanted) */
+  uint8_t* rho_out;         /* in: 32 B, receives rho in standard form LE */
+  uint8_t* folded_out;      /* in: 128 B, receives A || B (affine LEM) of the first (whole-batch) check */
+  uint8_t* interp_out;      /* in: l x 32 B, receives D (Montgomery) of the first check */
+  uint32_t pairing_checks;  /* out: 2-pair pairing checks performed */
+  int on_gpu;               /* out: 1 if the folds ran on the GPU */
+  double hash_ms, fold_ms, pairing_ms; /* out: wall clock of the seed and rho, of all folds (structural checks
+                                          and transfers included), of all pairing checks */
+} kgs_coset_batch_diag_t;
+int kgs_kzg_verify_cosets_batch(kgs_ctx_t* ctx, int nbits, int lbits, const uint8_t* commits_lem, uint64_t ncommits,
+                                const uint32_t* commit_of, const uint64_t* index, const uint8_t* ys_mont,
+                                const uint8_t* proofs_lem, uint64_t count, const uint8_t* srs_g1_lem,
+                                const uint8_t tau_l_g2[128], const uint8_t* seed32, uint8_t* valid_out,
+                                kgs_coset_batch_diag_t* diag);
+/* Same with d_commit_of, d_index, d_ys_mont and d_proofs_lem device pointers (on ctx's device, only read; e.g.
+ * kgs_kzg_open_cosets_device's outputs). commits_lem, srs_g1_lem, tau_l_g2, valid_out and diag stay host
+ * pointers. ctx and seed32 must not be NULL (the seed is not derived from device memory); the folds always run
+ * on the GPU. */
+int kgs_kzg_verify_cosets_batch_device(kgs_ctx_t* ctx, int nbits, int lbits, const uint8_t* commits_lem,
+                                       uint64_t ncommits, const void* d_commit_of, const void* d_index,
+                                       const void* d_ys_mont, const void* d_proofs_lem, uint64_t count,
+                                       const uint8_t* srs_g1_lem, const uint8_t tau_l_g2[128], const uint8_t* seed32,
+                                       uint8_t* valid_out, kgs_coset_batch_diag_t* diag);
+/* The weighted sum of interpolants on its own: out_mont[j] = sum_{k < count} weights[k] * w^(-index[k] j) * J_{k,j},
+ * j < l, with J_k the inverse transform of size l of row k of ys_mont (kgs_ntt's convention, 1 / l included); with
+ * count == 1 and weight one this is the coefficient vector of kgs_kzg_verify_coset's I. A row of weight zero is not
+ * read. weights_mont: count x 32 B Montgomery. nbits / lbits / count ranges as above; with a context lbits <= 10
+ * (one fused kernel, coset_fold.hip k_coset_interp_fold; larger l: KGS_E_ARG), ctx == NULL computes on the host.
+ * KGS_E_ARG also for a NULL buffer with work to do, an index >= m, a weight or (in a row of nonzero weight) a value
+ * >= r, a rank group, MSM sharding. count == 0 gives zeros. Context contract as above. */
+int kgs_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const uint64_t* index, const uint8_t* ys_mont,
+                          const uint8_t* weights_mont, uint64_t count, uint8_t* out_mont /* l x 32 B */);
+/* Same with device pointers (on ctx's device; ctx must not be NULL). The inputs are only read. */
+int kgs_coset_interp_fold_device(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                 const void* d_weights_mont, uint64_t count, void* d_out_mont);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -755,6 +845,11 @@ int kgs_bench_kzg_open_cosets(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t 
  * inverse NTT, kgs_msm over the resident window tables (profiles/g1_ntt_time.py times both by the wall
  * clock; each ends synchronised). */
 int kgs_bench_coeff_commit(kgs_ctx_t* ctx, const void* d_evals_std, int nbits, uint8_t out_lem[64]);
+/* `reps` runs (after one warm-up) of kgs_coset_interp_fold_device's two launches (k_coset_interp_fold and the
+ * reduction of its partial sums) over device-resident inputs, each between two events on ctx's stream: ms[r] =
+ * run r. count >= 1, lbits <= 10; the sum itself is discarded. */
+int kgs_bench_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                const void* d_weights_mont, uint64_t count, int reps, double* ms);
 /* Host-only test hook of kgs_prove's staging copy (no GPU): copies len bytes src -> dst the way a
  * host input vector is staged (256 KiB pieces over the copy pool, spans of `span` bytes reported in
  * order once copied). spans_out[i] receives the byte offset of the i-th reported span (up to max);

@@ -57,6 +57,13 @@ class BatchDiag(ctypes.Structure):
                 ("pairing_ms", ctypes.c_double)]
 
 
+class CosetBatchDiag(ctypes.Structure):
+    """kgs_coset_batch_diag_t (include/kgs.h)."""
+    _fields_ = [("rho_out", ctypes.c_void_p), ("folded_out", ctypes.c_void_p), ("interp_out", ctypes.c_void_p),
+                ("pairing_checks", ctypes.c_uint32), ("on_gpu", ctypes.c_int), ("hash_ms", ctypes.c_double),
+                ("fold_ms", ctypes.c_double), ("pairing_ms", ctypes.c_double)]
+
+
 MAX_ARGS = 16
 
 
@@ -194,6 +201,14 @@ def lib():
         L.kgs_kzg_open_cosets_cached.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.kgs_kzg_verify_coset.argtypes = [c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, c_u8p, c_u8p, c_u8p,
                                            c_u8p]
+        L.kgs_kzg_verify_cosets_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_u8p, ctypes.c_uint64,
+                                                  ctypes.c_void_p, ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64, c_u8p,
+                                                  c_u8p, c_u8p, c_u8p, ctypes.POINTER(CosetBatchDiag)]
+        L.kgs_kzg_verify_cosets_batch_device.argtypes = L.kgs_kzg_verify_cosets_batch.argtypes
+        L.kgs_coset_interp_fold.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_u8p, c_u8p,
+                                            ctypes.c_uint64, c_u8p]
+        L.kgs_coset_interp_fold_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         L.kgs_ptau_read_tau_g2_pow.argtypes = [ctypes.c_char_p, ctypes.c_uint64, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -857,6 +872,38 @@ class Context:
         Montgomery coefficients, read only; d_proofs to 2^(nbits - lbits) x 64 writable bytes; d_evals to
         2^nbits x 32 writable bytes, or None."""
         _check(lib().kgs_kzg_open_cosets_device(self._h, d_coef, n, nbits, lbits, d_proofs, d_evals))
+
+    def kzg_verify_cosets_batch(self, tau_l_g2, srs_g1, nbits, lbits, commits, openings, locate=True, seed=None,
+                                diag=None):
+        """Batch verifier for coset openings (kgs_kzg_verify_cosets_batch) with the folds on this context's GPU:
+        see the module-level kzg_verify_cosets_batch."""
+        return _kzg_verify_cosets_batch(self._h, tau_l_g2, srs_g1, nbits, lbits, commits, openings, locate, seed, diag)
+
+    def kzg_verify_cosets_batch_device(self, tau_l_g2, srs_g1, nbits, lbits, commits, d_commit_of, d_index, d_ys,
+                                       d_proofs, count, seed, locate=True, diag=None):
+        """Device-resident twin (kgs_kzg_verify_cosets_batch_device): d_commit_of (count x uint32), d_index (count x
+        uint64), d_ys (count * 2^lbits x 32 B Montgomery) and d_proofs (count x 64 B) are device pointers (ints),
+        only read; commits (a list of 64 B points, or their concatenation), srs_g1 and tau_l_g2 are host bytes.
+        seed: 32 bytes, unpredictable to whoever made the proofs (required: nothing on the device is hashed).
+        Returns a list of count bools, or one bool with locate=False."""
+        if seed is None or len(seed) != 32:
+            raise ValueError("the device twin needs a 32-byte seed")
+        commits = _commit_bytes(commits)
+        l = 1 << lbits if 0 <= lbits <= 28 else 0
+        if len(srs_g1) < 64 * l:
+            raise ValueError("srs_g1 must hold at least 2^lbits x 64 bytes")
+        return _coset_batch_call(lib().kgs_kzg_verify_cosets_batch_device, self._h, tau_l_g2, srs_g1, nbits, lbits,
+                                 commits, d_commit_of, d_index, d_ys, d_proofs, count, seed, locate, diag)
+
+    def coset_interp_fold(self, nbits, lbits, index, ys_mont, weights_mont):
+        """The weighted sum of interpolants on the GPU (kgs_coset_interp_fold): see the module-level
+        coset_interp_fold."""
+        return _coset_interp_fold(self._h, nbits, lbits, index, ys_mont, weights_mont)
+
+    def coset_interp_fold_device(self, nbits, lbits, d_index, d_ys, d_weights, count, d_out):
+        """Device-resident twin (kgs_coset_interp_fold_device): device pointers (ints) to count x uint64 indices,
+        count * 2^lbits x 32 B values, count x 32 B weights, all only read, and 2^lbits x 32 writable bytes."""
+        _check(lib().kgs_coset_interp_fold_device(self._h, nbits, lbits, d_index, d_ys, d_weights, count, d_out))
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1543,6 +1590,115 @@ def kzg_verify_coset(tau_l_g2, srs_g1, commit, nbits, lbits, index, ys_mont, pro
         tau_l_g2 = ptau_read_tau_g2_pow(tau_l_g2, l)
     return _check(lib().kgs_kzg_verify_coset(_buf(commit), nbits, lbits, index, _buf(ys_mont), _buf(proof),
                                              _buf(srs_g1[:64 * l]), _buf(tau_l_g2))) == 1
+
+
+def _commit_bytes(commits):
+    if isinstance(commits, (bytes, bytearray, memoryview)):
+        data = bytes(commits)
+    else:
+        commits = [bytes(c) for c in commits]
+        if any(len(c) != 64 for c in commits):
+            raise ValueError("a commitment holds 64 bytes")
+        data = b"".join(commits)
+    if len(data) % 64:
+        raise ValueError("commits must hold 64-byte points")
+    return data
+
+
+def _coset_batch_call(fn, handle, tau_l_g2, srs_g1, nbits, lbits, commits, commit_of, index, ys, proofs, count, seed,
+                      locate, diag):
+    l = 1 << lbits if 0 <= lbits <= 28 else 0
+    if isinstance(tau_l_g2, (str, os.PathLike)) or len(tau_l_g2) != 128:
+        tau_l_g2 = ptau_read_tau_g2_pow(tau_l_g2, l)
+    valid = ctypes.create_string_buffer(max(count, 1)) if locate else None
+    d = CosetBatchDiag()
+    rho = fo = it = None
+    if diag is not None:
+        rho, fo, it = ctypes.create_string_buffer(32), ctypes.create_string_buffer(128), \
+            ctypes.create_string_buffer(32 * max(l, 1))
+        d.rho_out, d.folded_out, d.interp_out = (ctypes.cast(x, ctypes.c_void_p) for x in (rho, fo, it))
+    rc = _check(fn(handle, nbits, lbits, _buf(commits) if commits else None, len(commits) // 64, commit_of, index, ys,
+                   proofs, count, _buf(srs_g1[:64 * l]), _buf(tau_l_g2), _buf(seed) if seed is not None else None,
+                   valid, ctypes.byref(d)))
+    if diag is not None:
+        diag.update(rho=rho.raw, folded=fo.raw, interp=it.raw, pairing_checks=d.pairing_checks, on_gpu=d.on_gpu,
+                    hash_ms=d.hash_ms, fold_ms=d.fold_ms, pairing_ms=d.pairing_ms)
+    if not locate:
+        return rc == 1
+    return [valid.raw[k] == 1 for k in range(count)]
+
+
+def _kzg_verify_cosets_batch(handle, tau_l_g2, srs_g1, nbits, lbits, commits, openings, locate, seed, diag):
+    commits = _commit_bytes(commits)
+    l = 1 << lbits if 0 <= lbits <= 28 else 0
+    if len(srs_g1) < 64 * l:
+        raise ValueError("srs_g1 must hold at least 2^lbits x 64 bytes")
+    if seed is not None and len(seed) != 32:
+        raise ValueError("seed holds 32 bytes")
+    openings = list(openings)
+    sent = []  # positions of the openings that reach the library
+    for pos, (ci, idx, ys, proof) in enumerate(openings):
+        if len(ys) == 32 * l and len(proof) == 64 and 0 <= ci < (1 << 32) and 0 <= idx < (1 << 64):
+            sent.append(pos)
+    n = len(sent)
+    cof = (ctypes.c_uint32 * max(n, 1))(*[openings[p][0] for p in sent])
+    index = (ctypes.c_uint64 * max(n, 1))(*[openings[p][1] for p in sent])
+    ys = _buf(b"".join(bytes(openings[p][2]) for p in sent)) if n else None
+    proofs = _buf(b"".join(bytes(openings[p][3]) for p in sent)) if n else None
+    got = _coset_batch_call(lib().kgs_kzg_verify_cosets_batch, handle, tau_l_g2, srs_g1, nbits, lbits, commits,
+                            ctypes.cast(cof, ctypes.c_void_p), ctypes.cast(index, ctypes.c_void_p), ys, proofs, n, seed,
+                            locate, diag)
+    if diag is not None:
+        diag["indices"] = sent
+    if not locate:
+        return got and n == len(openings)
+    out = [False] * len(openings)
+    for j, pos in enumerate(sent):
+        out[pos] = got[j]
+    return out
+
+
+def kzg_verify_cosets_batch(tau_l_g2_or_ptau, srs_g1, nbits, lbits, commits, openings, device=0, locate=True, seed=None,
+                            diag=None):
+    """Verify many coset openings against one SRS with ONE pairing check (include/kgs.h
+    kgs_kzg_verify_cosets_batch). tau_l_g2_or_ptau: [tau^l]_2 as 128 B LEM, or the name of a ptau file to read it
+    from; srs_g1: the first 2^lbits points [tau^k]_1 (64 B affine LEM each, more are ignored); commits: a list of
+    64 B commitments (or their concatenation); openings: a sequence of (commit_index, coset_index, ys_mont, proof)
+    with ys_mont the 2^lbits values of the coset (32 B Montgomery each) and proof 64 B affine LEM, as
+    kzg_open_cosets gives them. Returns a list of bool, opening for opening what kzg_verify_coset returns; an
+    opening with ys_mont or proof of the wrong length is False without reaching the library.
+    device: the GPU whose context folds the batch; None computes on the host (no GPU). locate=False stops after
+    the aggregate check and returns one bool (all valid). seed: None derives the weights from a hash of the whole
+    batch; 32 bytes of the caller's replace that hash and must be unpredictable to whoever made the proofs.
+    diag: a dict that receives indices (positions of the openings sent to the library), rho (32 B standard form),
+    folded (A || B of the whole-batch check), interp (D, 2^lbits x 32 B Montgomery), pairing_checks, on_gpu,
+    hash_ms, fold_ms, pairing_ms."""
+    handle = None if device is None else _context(device).handle
+    return _kzg_verify_cosets_batch(handle, tau_l_g2_or_ptau, srs_g1, nbits, lbits, commits, openings, locate, seed,
+                                    diag)
+
+
+def _coset_interp_fold(handle, nbits, lbits, index, ys_mont, weights_mont):
+    index = list(index)
+    count = len(index)
+    l = 1 << lbits if 0 <= lbits <= 28 else 0
+    if len(ys_mont) != 32 * l * count or len(weights_mont) != 32 * count:
+        raise ValueError("ys_mont holds len(index) * 2^lbits and weights_mont len(index) 32-byte elements")
+    idx = (ctypes.c_uint64 * max(count, 1))(*index)
+    out = ctypes.create_string_buffer(32 * max(l, 1))
+    _check(lib().kgs_coset_interp_fold(handle, nbits, lbits, ctypes.cast(idx, ctypes.c_void_p),
+                                       _buf(ys_mont) if count else None, _buf(weights_mont) if count else None, count,
+                                       out))
+    return out.raw[:32 * l]
+
+
+def coset_interp_fold(nbits, lbits, index, ys_mont, weights_mont, device=0):
+    """D_j = sum_k weights[k] * w^(-index[k] j) * J_{k,j}, j < 2^lbits (kgs_coset_interp_fold): J_k is the inverse
+    transform of size 2^lbits of row k of ys_mont (32 B Montgomery values, the rows contiguous), w = Fr.w[nbits];
+    weights_mont holds one 32 B Montgomery weight per row. With one row of weight one this is the interpolant of
+    kzg_verify_coset. Returns 2^lbits x 32 B Montgomery. device=None computes on the host."""
+    handle = None if device is None else _context(device).handle
+    return _coset_interp_fold(handle, nbits, lbits, index, ys_mont, weights_mont)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

@@ -1,4 +1,4 @@
-// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip, g1ntt.hip). All pointers are device
+// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip, g1ntt.hip, coset_fold.hip). All pointers are device
 // pointers to 32 B Montgomery Fr elements (uint32_t[8]) or 64 B affine / 128 B XYZZ G1 points,
 // unless stated otherwise. Launches are asynchronous on `st`.
 #pragma once
@@ -263,5 +263,41 @@ void launch_bitrev_blocks(hipStream_t st, uint32_t* out, const uint32_t* in, int
 // in reverse order, each block in its own order (npts a multiple of the block)
 void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed = false,
                       int block_log = 0);
+
+
+// coset_fold.hip (the batch verifier for coset openings)
+// The fused interpolation fold covers l = 2^lbits up to 2^COSET_FOLD_LBITS_MAX values per row (32 KiB of LDS).
+constexpr int COSET_FOLD_LBITS_MAX = 10;
+// blocks of the fold over `count` rows: one per tile of max(1, 512 / l) rows, at most 1024
+inline unsigned coset_fold_blocks(uint64_t count, int lbits) {
+  const uint64_t rt = lbits < 9 ? 512u >> lbits : 1, tiles = (count + rt - 1) / rt;
+  return (unsigned)(tiles < 1 ? 1 : tiles > 1024 ? 1024 : tiles);
+}
+// bytes of launch_coset_interp_fold's `part`
+inline uint64_t coset_fold_part_bytes(uint64_t count, int lbits) {
+  return 32ull * coset_fold_blocks(count, lbits) * ((1ull << lbits) > 256 ? (1ull << lbits) : 256);
+}
+// out[j] (Montgomery) = sum_{k < count} weights[k] * w^(-index[k] j) * J_{k,j}, j < l = 2^lbits, with w = Fr.w[nbits]
+// and J_k the inverse transform of size l (kgs_ntt's convention, 1 / l included) of the l values of row k of ys
+// (count x l Montgomery elements, rows contiguous). A row with weight 0 is not read. valid: NULL, or count bytes:
+// a row with 0 there is skipped. A row with a value or a weight >= r or an index >= 2^(nbits - lbits) is skipped too, gets 0
+// in `valid` and sets *bad (a device word the caller has zeroed) to 1. tw_inv / invm: the domain's tables,
+// covering 2^nbits. Returns false, with nothing launched, for lbits outside 0 .. min(COSET_FOLD_LBITS_MAX, nbits).
+bool launch_coset_interp_fold(hipStream_t st, uint32_t* out, uint32_t* part, uint8_t* valid, uint32_t* bad,
+                              const uint32_t* ys, const uint64_t* index, const uint32_t* weights, uint64_t count,
+                              const uint32_t* tw_inv, const uint32_t* invm, int nbits, int lbits);
+// ok[i] = 1 if point i (64 B affine LEM) is the identity or has canonical coordinates on y^2 = x^3 + 3, else 0
+void launch_g1_on_curve(hipStream_t st, uint8_t* ok, const uint32_t* points, uint64_t n);
+// valid[k] = proof_ok[k] && commit_of[k] < ncommits && commit_ok[commit_of[k]] && index[k] < m, k < count
+void launch_coset_screen(hipStream_t st, uint8_t* valid, const uint8_t* proof_ok, const uint8_t* commit_ok,
+                         const uint32_t* commit_of, const uint64_t* index, uint64_t count, uint64_t ncommits,
+                         uint64_t m);
+// The 3 cnt + l terms of the openings lo <= k < lo + cnt (standard-form scalars, 64 B points): w_k pi_k (the cnt
+// terms of A), then B's: w_k C_c(k), w_k a_{i_k} pi_k, and -D_j srs_j for j < l (two launches: k_coset_terms,
+// k_coset_terms_srs). Openings with valid[k] == 0 give zero scalars and identities. tw_fwd covers 2^(nbits - lbits).
+void launch_coset_terms(hipStream_t st, uint32_t* scal, uint32_t* pts, const uint8_t* valid, const uint32_t* weights,
+                        const uint64_t* index, const uint32_t* commit_of, const uint32_t* commits,
+                        const uint32_t* proofs, const uint32_t* D, const uint32_t* srs, const uint32_t* tw_fwd,
+                        uint64_t lo, uint64_t cnt, int nbits, int lbits);
 
 }  // namespace kgs

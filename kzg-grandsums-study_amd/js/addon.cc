@@ -304,6 +304,7 @@ struct Job {
                // 8 = the G1 transform (g1Ntt), 9 = a commitment from evaluations (commitEvals)
                // 10 = every opening of a polynomial on its domain (kzgOpenAll)
                // 11 = every coset opening of a polynomial (kzgOpenCosets)
+               // 12 = a batch of coset openings against one SRS (kzgVerifyCosetsBatch)
   int rc = 0;
   std::string err;
   // load
@@ -335,6 +336,12 @@ struct Job {
   std::vector<std::vector<uint8_t>> vb_bytes;
   std::vector<uint8_t> vb_valid;
   kgs_batch_diag_t vb_diag = {};
+  // kzgVerifyCosetsBatch: nbits / ntt_inverse = nBits / lBits; the commitments in `com`, commit_of / index /
+  // the values / the proofs (copied), the SRS points in `bases`, [tau^l]_2 in `scal`, the seed (32 B or empty)
+  std::vector<uint32_t> cb_commit_of;
+  std::vector<uint64_t> cb_index;
+  std::vector<uint8_t> cb_ys, cb_proofs, cb_seed;
+  kgs_coset_batch_diag_t cb_diag = {};
   // proveMulti: the arguments' kinds and borrowed input views
   struct MultiArg {
     int kind = 0;
@@ -525,6 +532,14 @@ static void job_execute(napi_env, void* data) {
     j->ev.resize((size_t)32 << j->ntt_logm);
     j->rc = kgs_kzg_open_cosets(j->ctx, j->scal.data(), j->scal.size() / 32, j->ntt_logm, j->ntt_inverse, j->bases.data(),
                                 j->ev.data());
+  } else if (j->op == 12) {
+    j->vb_valid.assign(j->cb_index.size() + 1, 0);
+    const int rc = kgs_kzg_verify_cosets_batch(j->ctx, j->nbits, j->ntt_inverse, j->com.data(), j->com.size() / 64,
+                                               j->cb_commit_of.data(), j->cb_index.data(), j->cb_ys.data(),
+                                               j->cb_proofs.data(), j->cb_index.size(), j->bases.data(), j->scal.data(),
+                                               j->cb_seed.empty() ? nullptr : j->cb_seed.data(), j->vb_valid.data(),
+                                               &j->cb_diag);
+    j->rc = rc < 0 ? rc : KGS_OK;
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -562,6 +577,21 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_create_object(env, &o);
     napi_set_named_property(env, o, "proofs", make_u8(env, j->bases.data(), j->bases.size()));
     napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
+    napi_resolve_deferred(env, j->deferred, o);
+  } else if (j->op == 12) {
+    napi_value o, v;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "valid", make_u8(env, j->vb_valid.data(), j->cb_index.size()));
+    napi_create_uint32(env, j->cb_diag.pairing_checks, &v);
+    napi_set_named_property(env, o, "pairingChecks", v);
+    napi_get_boolean(env, j->cb_diag.on_gpu != 0, &v);
+    napi_set_named_property(env, o, "onGpu", v);
+    napi_create_double(env, j->cb_diag.hash_ms, &v);
+    napi_set_named_property(env, o, "hashMs", v);
+    napi_create_double(env, j->cb_diag.fold_ms, &v);
+    napi_set_named_property(env, o, "foldMs", v);
+    napi_create_double(env, j->cb_diag.pairing_ms, &v);
+    napi_set_named_property(env, o, "pairingMs", v);
     napi_resolve_deferred(env, j->deferred, o);
   } else if (j->op == 6) {
     napi_value o, v;
@@ -1202,6 +1232,62 @@ static napi_value KzgVerifyCoset(napi_env env, napi_callback_info info) {
   return out;
 }
 
+// kzgVerifyCosetsBatch(ctx | null, nBits, lBits, commits, commitOf, index, ysMont, proofs, srsG1, tauLG2, seed | null)
+//   -> Promise<{valid, pairingChecks, onGpu, hashMs, foldMs, pairingMs}> (kgs_kzg_verify_cosets_batch): commits the
+// concatenated 64 B commitments, commitOf / index arrays of count numbers, ysMont count * 2^lBits x 32 B, proofs
+// count x 64 B, srsG1 at least 2^lBits x 64 B, tauLG2 128 B, seed 32 B or null; ctx null: on the host
+static napi_value KzgVerifyCosetsBatch(napi_env env, napi_callback_info info) {
+  size_t argc = 11;
+  napi_value argv[11];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 12;
+  napi_valuetype vt = napi_null;
+  napi_typeof(env, argv[0], &vt);
+  j->ctx = vt == napi_null || vt == napi_undefined ? nullptr : get_ctx(env, argv[0]);
+  int32_t nbits = -1, lbits = -1;
+  napi_get_value_int32(env, argv[1], &nbits);
+  napi_get_value_int32(env, argv[2], &lbits);
+  j->nbits = nbits;
+  j->ntt_inverse = lbits;
+  j->com = bytes_of(env, argv[3]);
+  uint32_t nc = 0, ni = 0;
+  napi_get_array_length(env, argv[4], &nc);
+  napi_get_array_length(env, argv[5], &ni);
+  bool ok = nc == ni && nbits >= 0 && nbits <= 28 && lbits >= 0 && lbits <= nbits;
+  for (uint32_t k = 0; ok && k < nc; k++) {
+    napi_value v;
+    int64_t c = -1, i = -1;
+    napi_get_element(env, argv[4], k, &v);
+    napi_get_value_int64(env, v, &c);
+    napi_get_element(env, argv[5], k, &v);
+    napi_get_value_int64(env, v, &i);
+    ok = c >= 0 && c <= 0xffffffffll && i >= 0;
+    j->cb_commit_of.push_back((uint32_t)c);
+    j->cb_index.push_back((uint64_t)i);
+  }
+  j->cb_ys = bytes_of(env, argv[6]);
+  j->cb_proofs = bytes_of(env, argv[7]);
+  j->bases = bytes_of(env, argv[8]);
+  j->scal = bytes_of(env, argv[9]);
+  napi_typeof(env, argv[10], &vt);
+  if (argc > 10 && vt != napi_null && vt != napi_undefined) j->cb_seed = bytes_of(env, argv[10]);
+  if (!ok || j->com.size() % 64 || j->cb_proofs.size() != (size_t)64 * nc ||
+      j->cb_ys.size() != ((size_t)32 * nc << lbits) || j->bases.size() < ((size_t)64 << lbits) || j->scal.size() != 128 ||
+      (!j->cb_seed.empty() && j->cb_seed.size() != 32)) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgVerifyCosetsBatch: expected 64 B commitments, count commit indices and coset indices, count * 2^lBits x 32 B values, count x 64 B proofs, at least 2^lBits x 64 B SRS points, 128 B [tau^l]_2, a 32 B seed or null");
+    return nullptr;
+  }
+  // the library takes NULL for an empty buffer; a vector's data() may be anything then
+  j->com.reserve(1);
+  j->cb_commit_of.reserve(1);
+  j->cb_index.reserve(1);
+  j->cb_ys.reserve(1);
+  j->cb_proofs.reserve(1);
+  return queue(env, j, "kgs_kzg_verify_cosets_batch");
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1240,6 +1326,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"kzgOpenAll", nullptr, KzgOpenAll, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgOpenCosets", nullptr, KzgOpenCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCoset", nullptr, KzgVerifyCoset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgVerifyCosetsBatch", nullptr, KzgVerifyCosetsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

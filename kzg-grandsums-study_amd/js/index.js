@@ -25,6 +25,10 @@ module.exports = {
     // tauLG2) -> bool checks one of them on the host (kgs_kzg_verify_coset)
     kzg_open_cosets: require("./src/backend").kzgOpenCosets,
     kzg_verify_coset: require("./src/backend").kzgVerifyCoset,
+    // kzg_verify_cosets_batch(commits, nBits, lBits, openings, srsG1, tauLG2[, {host, seed}]) -> Promise<{valid, ..}>:
+    // many coset openings {commit, index, ys, proof} against one SRS with one pairing check, folded on the GPU
+    // (kgs_kzg_verify_cosets_batch)
+    kzg_verify_cosets_batch: require("./src/backend").kzgVerifyCosetsBatch,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

@@ -258,6 +258,32 @@ function kzgVerifyCoset(commit, nBits, lBits, index, ysMont, proof, srsG1, tauLG
         contiguous(srsG1), contiguous(tauLG2));
 }
 
+// Many coset openings against one SRS with one pairing check (kgs_kzg_verify_cosets_batch)
+// -> Promise<{valid: [bool ..], pairingChecks, onGpu, hashMs, foldMs, pairingMs}>. commits: an array of 64 B affine
+// LEM commitments; openings: an array of {commit (an index into commits), index (the coset), ys (2^lBits x 32 B
+// Montgomery), proof (64 B affine LEM)}; srsG1: the first 2^lBits points [tau^k]_1; tauLG2: [tau^(2^lBits)]_2,
+// 128 B LEM. opts.host computes on the host (no GPU), else the folds run on a pooled context's GPU; opts.seed:
+// 32 bytes that replace the hash of the batch as the source of the weights (they must be unpredictable to
+// whoever made the proofs). An opening with ys or proof of the wrong length is false without reaching the library.
+async function kzgVerifyCosetsBatch(commits, nBits, lBits, openings, srsG1, tauLG2, opts) {
+    opts = opts || {};
+    const cm = Buffer.concat(commits.map(c => Buffer.from(contiguous(c))));
+    const sent = [];
+    openings.forEach((o, k) => {
+        if (contiguous(o.ys).byteLength === 32 * 2 ** lBits && contiguous(o.proof).byteLength === 64) sent.push(k);
+    });
+    const ys = Buffer.concat(sent.map(k => Buffer.from(contiguous(openings[k].ys))));
+    const proofs = Buffer.concat(sent.map(k => Buffer.from(contiguous(openings[k].proof))));
+    const args = [nBits, lBits, new Uint8Array(cm), sent.map(k => openings[k].commit), sent.map(k => openings[k].index),
+        new Uint8Array(ys), new Uint8Array(proofs), contiguous(srsG1), contiguous(tauLG2),
+        opts.seed ? contiguous(opts.seed) : null];
+    const res = opts.host ? await load().kzgVerifyCosetsBatch(null, ...args)
+        : await withContext(slot => load().kzgVerifyCosetsBatch(slot.ctx, ...args));
+    const valid = openings.map(() => false);
+    sent.forEach((k, j) => { valid[k] = res.valid[j] === 1; });
+    return Object.assign(res, { valid });
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -310,4 +336,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, kzgVerifyCosetsBatch, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
