@@ -806,6 +806,31 @@ int kgs_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const uint64_t* 
 /* Same with device pointers (on ctx's device; ctx must not be NULL). The inputs are only read. */
 int kgs_coset_interp_fold_device(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
                                  const void* d_weights_mont, uint64_t count, void* d_out_mont);
+/* ---- recovery: a polynomial of known length back from a subset of its cosets. Notation as for
+ * kgs_kzg_open_cosets: n = 2^nbits, l = 2^lbits, m = n / l, w = Fr.w[nbits], coset i < m is { w^(i + m j) : j < l }.
+ * Row k < count of ys_mont holds the l values y_{k,j} = p(w^(index[k] + m j)) (kgs_kzg_verify_cosets_batch's rows);
+ * the indices are distinct, in any order. With count l >= len there is at most one p of degree < len through
+ * those values:
+ *   returns 1  it exists: coef_mont receives its len coefficients, and evals_mont (if not NULL) all n values p(w^k)
+ *              in natural order, as kgs_kzg_open_cosets' evals_mont holds them
+ *   returns 0  the values lie on no polynomial of degree < len; the outputs are unspecified
+ * Fr only: no SRS, no G1, no pairing; a context with no SRS loaded serves. With Z the vanishing polynomial of the
+ * missing cosets (a polynomial in X^l, built as a product tree on the device): three transforms of size n (E Z to
+ * coefficients, onto the coset g <w>, back after the division by Z there), two of size m and m inversions.
+ *   nbits  0 .. 23;  lbits  0 .. nbits;  len  1 .. n;  count  ceil(len / l) .. m
+ *   index  count coset indices < m;  ys_mont  count x l x 32 B Montgomery, canonical;  both only read
+ * KGS_E_ARG (kgs_last_error names the first offender where there is one): ctx == NULL (there is no host path; no
+ * GPU is touched), a NULL index, ys_mont or coef_mont, nbits / lbits / len / count out of range, an index >= m, an
+ * index given twice, a value >= r, a rank group, MSM sharding. Context contract as for kgs_kzg_open_cosets: device
+ * work buffers of the call's own ("rc_*"), the shared domain tables may grow to 2^nbits; the window tables, the
+ * Lagrange, kgs_kzg_open_all and kgs_kzg_open_cosets caches and the prover's buffers are not touched; the context
+ * is idle on return, on error paths too. */
+int kgs_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const uint64_t* index, const uint8_t* ys_mont,
+                           uint64_t count, uint64_t len, uint8_t* coef_mont /* len x 32 B */,
+                           uint8_t* evals_mont /* NULL or 2^nbits x 32 B */);
+/* Same with device pointers (on ctx's device) for index, ys, coef and evals. */
+int kgs_kzg_recover_cosets_device(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                  uint64_t count, uint64_t len, void* d_coef_mont, void* d_evals_mont);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -850,6 +875,14 @@ int kgs_bench_coeff_commit(kgs_ctx_t* ctx, const void* d_evals_std, int nbits, u
  * run r. count >= 1, lbits <= 10; the sum itself is discarded. */
 int kgs_bench_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
                                 const void* d_weights_mont, uint64_t count, int reps, double* ms);
+/* `reps` runs of a leg of kgs_kzg_recover_cosets_device over device-resident inputs (arguments and ranges as that
+ * call's; d_coef_mont receives the coefficients), after one whole call, each between two events on ctx's stream:
+ * ms[r] = run r. what: 0 the whole call without evaluations, 1 the marks and the product tree, 2 the m-sized side
+ * (z's coefficients, its two transforms of size m, the batch inversion), 3 the three transforms of size n alone.
+ * leaf_log: the tree's leaves cover 2^leaf_log cosets, 6 .. 9, or 0 for the library's choice. */
+int kgs_bench_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                 uint64_t count, uint64_t len, void* d_coef_mont, int what, int leaf_log, int reps,
+                                 double* ms);
 /* Host-only test hook of kgs_prove's staging copy (no GPU): copies len bytes src -> dst the way a
  * host input vector is staged (256 KiB pieces over the copy pool, spans of `span` bytes reported in
  * order once copied). spans_out[i] receives the byte offset of the i-th reported span (up to max);

@@ -209,6 +209,15 @@ def lib():
                                             ctypes.c_uint64, c_u8p]
         L.kgs_coset_interp_fold_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.kgs_kzg_recover_cosets.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, c_u8p,
+                                             ctypes.c_uint64, ctypes.c_uint64, c_u8p, c_u8p]
+        L.kgs_kzg_recover_cosets_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                    ctypes.c_void_p]
+        L.kgs_bench_kzg_recover_cosets.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_double)]
         L.kgs_ptau_read_tau_g2_pow.argtypes = [ctypes.c_char_p, ctypes.c_uint64, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -904,6 +913,18 @@ class Context:
         """Device-resident twin (kgs_coset_interp_fold_device): device pointers (ints) to count x uint64 indices,
         count * 2^lbits x 32 B values, count x 32 B weights, all only read, and 2^lbits x 32 writable bytes."""
         _check(lib().kgs_coset_interp_fold_device(self._h, nbits, lbits, d_index, d_ys, d_weights, count, d_out))
+
+    def kzg_recover_cosets(self, nbits, lbits, index, ys_mont, length, evals=False):
+        """A polynomial of `length` coefficients back from a subset of its cosets (kgs_kzg_recover_cosets): see
+        the module-level kzg_recover_cosets."""
+        return _kzg_recover_cosets(self._h, nbits, lbits, index, ys_mont, length, evals)
+
+    def kzg_recover_cosets_device(self, nbits, lbits, d_index, d_ys, count, length, d_coef, d_evals=None):
+        """Device-resident twin (kgs_kzg_recover_cosets_device): device pointers (ints) to count x uint64 coset
+        indices and count * 2^lbits x 32 B Montgomery values, both only read, to length x 32 writable bytes and,
+        or None, to 2^nbits x 32 writable bytes. Returns the verdict as a bool."""
+        return _check(lib().kgs_kzg_recover_cosets_device(self._h, nbits, lbits, d_index, d_ys, count, length, d_coef,
+                                                          d_evals)) == 1
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1699,6 +1720,33 @@ def coset_interp_fold(nbits, lbits, index, ys_mont, weights_mont, device=0):
     kzg_verify_coset. Returns 2^lbits x 32 B Montgomery. device=None computes on the host."""
     handle = None if device is None else _context(device).handle
     return _coset_interp_fold(handle, nbits, lbits, index, ys_mont, weights_mont)
+
+
+def _kzg_recover_cosets(handle, nbits, lbits, index, ys_mont, length, evals):
+    index = list(index)
+    count = len(index)
+    ok = 0 <= nbits <= 23 and 0 <= lbits <= nbits  # else the library refuses before it reads or writes
+    if ok and len(ys_mont) != (32 << lbits) * count:
+        raise ValueError("ys_mont holds len(index) * 2^lbits 32-byte elements")
+    idx = (ctypes.c_uint64 * max(count, 1))(*index)
+    fits = ok and 1 <= length <= 1 << nbits
+    coef = ctypes.create_string_buffer(32 * length if fits else 32)
+    ev = ctypes.create_string_buffer(32 << nbits if ok else 32) if evals else None
+    py, ky = _ptr(ys_mont) if len(ys_mont) else (None, None)  # read in place
+    rc = _check(lib().kgs_kzg_recover_cosets(handle, nbits, lbits, ctypes.cast(idx, ctypes.c_void_p), py, count, length,
+                                             coef, ev))
+    del ky
+    return (rc == 1, coef.raw, ev.raw) if evals else (rc == 1, coef.raw)
+
+
+def kzg_recover_cosets(nbits, lbits, index, ys_mont, length, evals=False, device=0):
+    """The polynomial of degree < length through the given cosets of the domain of 2^nbits points
+    (kgs_kzg_recover_cosets): index holds distinct coset indices < m = 2^(nbits - lbits), in any order, and row k of
+    ys_mont the 2^lbits Montgomery values p(w^(index[k] + m j)), as kzg_open_cosets' evaluations give them;
+    len(index) * 2^lbits >= length. Returns (ok, coefs) or with evals=True (ok, coefs, evals): length x 32 B
+    Montgomery coefficients and p(w^k) in natural order. ok is False when the values lie on no polynomial of
+    degree < length; the other results then mean nothing. Needs no SRS."""
+    return _kzg_recover_cosets(_context(device).handle, nbits, lbits, index, ys_mont, length, evals)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

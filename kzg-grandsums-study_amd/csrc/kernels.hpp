@@ -1,4 +1,4 @@
-// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip, g1ntt.hip, coset_fold.hip). All pointers are device
+// Launch wrappers for the gfx950 kernels (ntt.hip, poly.hip, msm.hip, lookup.hip, fold.hip, g1ntt.hip, coset_fold.hip, recover.hip). All pointers are device
 // pointers to 32 B Montgomery Fr elements (uint32_t[8]) or 64 B affine / 128 B XYZZ G1 points,
 // unless stated otherwise. Launches are asynchronous on `st`.
 #pragma once
@@ -81,6 +81,12 @@ void ntt_dif(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t in_len,
              const uint32_t* tw, int logM);
 void ntt_dit(hipStream_t st, uint32_t* out, const uint32_t* in, int in_bitrev, int logm, const uint32_t* tw, int logM,
              const uint32_t* post, const uint32_t* post_s);
+// The 2^(logtotal - s) transforms of size 2^s (1 <= s <= logtotal) over the consecutive blocks of 2^s elements of
+// `data` (2^logtotal elements), in place: the last s stages of ntt_dif / the first s stages of ntt_dit over the
+// whole array, by the same passes. dif: natural in, bit-reversed out within each block; dit: bit-reversed in,
+// natural out, every output times *post_s if given. tw: a stage table covering 2^s.
+void ntt_dif_blocks(hipStream_t st, uint32_t* data, int logtotal, int s, const uint32_t* tw);
+void ntt_dit_blocks(hipStream_t st, uint32_t* data, int logtotal, int s, const uint32_t* tw, const uint32_t* post_s);
 void launch_powers(hipStream_t st, uint32_t* out, uint64_t count, const uint32_t* w_dev, const uint32_t* scale_dev);
 void launch_scale_copy(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t n, const uint32_t* tab,
                        const uint32_t* sc);
@@ -299,5 +305,39 @@ void launch_coset_terms(hipStream_t st, uint32_t* scal, uint32_t* pts, const uin
                         const uint64_t* index, const uint32_t* commit_of, const uint32_t* commits,
                         const uint32_t* proofs, const uint32_t* D, const uint32_t* srs, const uint32_t* tw_fwd,
                         uint64_t lo, uint64_t cnt, int nbits, int lbits);
+
+// recover.hip (kgs_kzg_recover_cosets). m = 2^logm cosets of l = 2^lbits points, n = m l.
+constexpr uint32_t RC_NONE = 0xFFFFFFFFu;  // row_of: the coset is missing
+// the call's four flag words: the lowest row with an index >= m, the lowest row that names a coset again, the
+// lowest value (row * l + j) >= r (each preset to RC_NONE), and 1 for a nonzero coefficient from len on (preset 0)
+constexpr int RC_FLAG_INDEX = 0, RC_FLAG_DUP = 1, RC_FLAG_VALUE = 2, RC_FLAG_HIGH = 3;
+// A leaf of the product tree covers 2^leaf_log coset slots (one thread each). A leaf costs B / 4 products per slot
+// at half the cosets missing, a tree level a constant; 64, 128 and 256 measured within a few per cent of each other
+// at every size, and 64 is the least arithmetic. The kernel is built for up to 512 (its LDS, below,
+// stays under the 64 KiB of a plain launch).
+constexpr int RC_LEAF_LOG = 6, RC_LEAF_LOG_MIN = 6, RC_LEAF_LOG_MAX = 9, RC_LEAF_MAX = 1 << RC_LEAF_LOG_MAX;
+inline unsigned rc_leaf_lds_bytes(int leaf_log) { return (6u * 16u + 4u) << leaf_log; }
+// row_of (m words preset to RC_NONE) and flags from the `count` coset indices
+void launch_rc_mark(hipStream_t st, uint32_t* row_of, uint32_t* flags, const uint64_t* index, uint64_t count, uint64_t m);
+// T (m elements): block b of 2^leaf_log elements = the low coefficients of Y^(B - d) prod (Y - a_i) over the d missing
+// slots of [b B, (b + 1) B), monic of degree B. leaf_log <= min(logm, RC_LEAF_LOG_MAX); tw_fwd covers m.
+void launch_rc_leaves(hipStream_t st, uint32_t* T, const uint32_t* row_of, const uint32_t* tw_fwd, int logm, int leaf_log);
+// One level: T's m / d monic polynomials of degree d = 2^logd (d low coefficients each) -> the m / 2d products of
+// neighbours, in place. W: 2m elements of work space. tw_fwd / tw_inv / invm cover 2d.
+void launch_rc_level(hipStream_t st, uint32_t* T, uint32_t* W, int logm, int logd, const uint32_t* tw_fwd,
+                     const uint32_t* tw_inv, const uint32_t* invm);
+// the root T = Y^count z(Y) -> zc[t] = z_t and zs[t] = z_t g^(l t), t < m (coset_pow covers n)
+void launch_rc_zcoef(hipStream_t st, uint32_t* zc, uint32_t* zs, const uint32_t* T, uint64_t count, uint64_t m,
+                     const uint32_t* coset_pow, int lbits);
+// out[i + m j] = ys[row_of[i] l + j] * zev[bitrev_m(i)], zero where row_of[i] == RC_NONE; a value >= r counts as
+// zero and lowers flags[RC_FLAG_VALUE] to its position
+void launch_rc_scatter(hipStream_t st, uint32_t* out, const uint32_t* ys, const uint32_t* row_of, const uint32_t* zev,
+                       uint32_t* flags, int logm, int lbits);
+// out[i] = 1 / in[i], i < n, zero for zero; out != in
+void launch_rc_batch_inv(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t n);
+// data[x] *= inv[x >> lbits], x < n
+void launch_rc_divide(hipStream_t st, uint32_t* data, const uint32_t* inv, int lbits, uint64_t n);
+// coef[j] = q[j] for j < len; flags[RC_FLAG_HIGH] = 1 if q[j] != 0 for some len <= j < n
+void launch_rc_check_copy(hipStream_t st, uint32_t* coef, const uint32_t* q, uint64_t len, uint64_t n, uint32_t* flags);
 
 }  // namespace kgs

@@ -1,0 +1,240 @@
+// kgs_kzg_recover_cosets (include/kgs.h; kernels in recover.hip): a polynomial of known length
+// back from a subset of its cosets. Fr only: no SRS, no G1, no pairing. Host: argument checks, the call's own
+// "rc_*" buffers in the context's pool, the launch sequence, and the reading of the four flag words at the end.
+// Every kernel's accesses are bounded whatever the flags say, so one drain at the end is the only one.
+#include <mutex>
+
+#include "context.hpp"
+
+namespace {
+
+constexpr int RC_NBITS_MAX = 23;  // what the shared domain tables cover
+
+struct RcBufs {
+  uint32_t *row_of, *flags, *T, *W, *zc, *zs, *zev, *zsh, *inv, *A, *R;
+};
+
+RcBufs rc_bufs(kgs_ctx& c, int nbits, int lbits) {
+  const uint64_t n = 1ull << nbits, m = n >> lbits;
+  RcBufs b;
+  b.row_of = c.buf("rc_row_of", 4 * m);
+  b.flags = c.buf("rc_flags", 64);
+  b.T = c.buf("rc_T", 32 * m);
+  b.W = c.buf("rc_W", 64 * m);
+  b.zc = c.buf("rc_zc", 32 * m);
+  b.zs = c.buf("rc_zs", 32 * m);
+  b.zev = c.buf("rc_zev", 32 * m);
+  b.zsh = c.buf("rc_zsh", 32 * m);
+  b.inv = c.buf("rc_inv", 32 * m);
+  b.A = c.buf("rc_A", 32 * n);
+  b.R = c.buf("rc_R", 32 * n);
+  return b;
+}
+
+int rc_leaf_log(int logm, int leaf_log) { return leaf_log < logm ? leaf_log : logm; }
+
+// the marks and the product tree: T = Y^count z(Y), the vanishing polynomial of the missing cosets in Y = X^l
+void rc_tree(kgs_ctx& c, const RcBufs& b, const uint64_t* d_index, uint64_t count, int logm, int leaf_log) {
+  const uint64_t m = 1ull << logm;
+  HC(hipMemsetAsync(b.row_of, 0xFF, 4 * m, c.st));
+  HC(hipMemsetAsync(b.flags, 0xFF, 12, c.st));
+  HC(hipMemsetAsync(b.flags + RC_FLAG_HIGH, 0, 4, c.st));
+  launch_rc_mark(c.st, b.row_of, b.flags, d_index, count, m);
+  const int ll = rc_leaf_log(logm, leaf_log);
+  launch_rc_leaves(c.st, b.T, b.row_of, c.tw_fwd, logm, ll);
+  for (int logd = ll; logd < logm; logd++) launch_rc_level(c.st, b.T, b.W, logm, logd, c.tw_fwd, c.tw_inv, c.invm);
+}
+
+// z(a_i) and 1 / z(g^l a_i), i < m, both at position bitrev(i): two transforms of size m and one batch inversion
+void rc_mside(kgs_ctx& c, const RcBufs& b, uint64_t count, int logm, int lbits) {
+  const uint64_t m = 1ull << logm;
+  launch_rc_zcoef(c.st, b.zc, b.zs, b.T, count, m, c.coset_pow, lbits);
+  ntt_dif(c.st, b.zev, b.zc, m, logm, nullptr, c.tw_fwd, c.logM);
+  ntt_dif(c.st, b.zsh, b.zs, m, logm, nullptr, c.tw_fwd, c.logM);
+  launch_rc_batch_inv(c.st, b.inv, b.zsh, m);
+}
+
+// the three transforms of size n with the division between the second and the third: A = E Z (natural) ->
+// R = its coefficients -> R on g <w> (bit-reversed) / Z there -> q (natural) in R
+void rc_nside(kgs_ctx& c, const RcBufs& b, int nbits, int lbits, bool divide = true) {
+  intt_nat(c, b.R, b.A, nbits);
+  coset_fwd(c, b.A, b.R, 1ull << nbits, nbits);
+  if (divide) launch_rc_divide(c.st, b.A, b.inv, lbits, 1ull << nbits);
+  ntt_dit(c.st, b.R, b.A, 1, nbits, c.tw_inv, c.logM, c.coset_ipow, c.invm + 8 * nbits);
+}
+
+// The whole call on device pointers, enqueued on the main stream (not synchronised). The caller holds the context,
+// has checked the arguments and grown the domain to 2^nbits.
+void rc_run(kgs_ctx& c, const RcBufs& b, int nbits, int lbits, const uint64_t* d_index, const uint32_t* d_ys, uint64_t count,
+            uint64_t len, uint32_t* d_coef, uint32_t* d_evals, int leaf_log = RC_LEAF_LOG) {
+  const int logm = nbits - lbits;
+  const uint64_t n = 1ull << nbits;
+  rc_tree(c, b, d_index, count, logm, leaf_log);
+  rc_mside(c, b, count, logm, lbits);
+  launch_rc_scatter(c.st, b.A, d_ys, b.row_of, b.zev, b.flags, logm, lbits);
+  rc_nside(c, b, nbits, lbits);
+  launch_rc_check_copy(c.st, d_coef, b.R, len, n, b.flags);
+  if (d_evals) {
+    ntt_dif(c.st, b.A, d_coef, len, nbits, nullptr, c.tw_fwd, c.logM);
+    launch_bitrev_copy(c.st, d_evals, b.A, nbits);
+  }
+  check_launch();
+}
+
+void rc_check_args(kgs_ctx_t* ctx, const char* fn, int nbits, int lbits, const void* index, const void* ys, uint64_t count,
+                   uint64_t len, const void* coef) {
+  if (!ctx) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL ctx (recovery has no host path)");
+  if (!index || !ys || !coef) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (nbits < 0 || nbits > RC_NBITS_MAX)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": nbits must be in 0 .. " + std::to_string(RC_NBITS_MAX));
+  if (lbits < 0 || lbits > nbits)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": lbits must be in 0 .. nbits = " + std::to_string(nbits));
+  const uint64_t n = 1ull << nbits, l = 1ull << lbits, m = n >> lbits;
+  if (len < 1 || len > n)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": len = " + std::to_string(len) + " must be in 1 .. 2^nbits = " + std::to_string(n));
+  const uint64_t need = (len + l - 1) >> lbits;
+  if (count < need || count > m)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": count = " + std::to_string(count) + " must be in ceil(len / l) = " +
+                                  std::to_string(need) + " .. m = " + std::to_string(m));
+}
+
+void rc_check_ctx(const kgs_ctx& c, const char* fn) {
+  if (c.group) throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context attached to a rank group.");
+  if (c.shard_world > 1)
+    throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context with MSM sharding (kgs_ctx_set_shard).");
+}
+
+// the flag words after the drain: the refusals they stand for, else the verdict
+int rc_verdict(kgs_ctx& c, const char* fn, const uint32_t* hf, const uint64_t* index, bool device, int nbits, int lbits) {
+  const uint64_t m = 1ull << (nbits - lbits);
+  auto index_at = [&](uint64_t k) {
+    uint64_t v = 0;
+    if (device)
+      HC(hipMemcpy(&v, index + k, 8, hipMemcpyDeviceToHost));
+    else
+      v = index[k];
+    return v;
+  };
+  if (hf[RC_FLAG_INDEX] != RC_NONE) {
+    const uint64_t k = hf[RC_FLAG_INDEX];
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": index[" + std::to_string(k) + "] = " + std::to_string(index_at(k)) +
+                                  " is not a coset of the domain (m = " + std::to_string(m) + ").");
+  }
+  if (hf[RC_FLAG_DUP] != RC_NONE) {
+    const uint64_t k = hf[RC_FLAG_DUP];
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": index[" + std::to_string(k) + "] = " + std::to_string(index_at(k)) +
+                                  " names a coset for the second time.");
+  }
+  if (hf[RC_FLAG_VALUE] != RC_NONE) {
+    const uint64_t e = hf[RC_FLAG_VALUE];
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": value " + std::to_string(e & ((1ull << lbits) - 1)) + " of row " +
+                                  std::to_string(e >> lbits) + " is not below r.");
+  }
+  (void)c;
+  return hf[RC_FLAG_HIGH] ? 0 : 1;
+}
+
+int recover_entry(kgs_ctx_t* ctx, int nbits, int lbits, const void* index, const void* ys, uint64_t count, uint64_t len,
+                  void* coef, void* evals, bool device) {
+  API_BEGIN
+  const char* fn = device ? "kgs_kzg_recover_cosets_device" : "kgs_kzg_recover_cosets";
+  rc_check_args(ctx, fn, nbits, lbits, index, ys, count, len, coef);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  rc_check_ctx(*ctx, fn);
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  const uint64_t n = 1ull << nbits, l = 1ull << lbits;
+  if (nbits > c.logM) ensure_domain(c, nbits);
+  const RcBufs b = rc_bufs(c, nbits, lbits);
+  uint32_t* hf = (uint32_t*)c.pin(16);
+  if (device) {
+    rc_run(c, b, nbits, lbits, (const uint64_t*)index, (const uint32_t*)ys, count, len, (uint32_t*)coef, (uint32_t*)evals);
+  } else {
+    uint64_t* di = (uint64_t*)c.buf("rc_index", 8 * count);
+    uint32_t* dy = c.buf("rc_ys", 32 * count * l);
+    uint32_t* dc = c.buf("rc_coef", 32 * len);
+    uint32_t* de = evals ? c.buf("rc_ev", 32 * n) : nullptr;
+    HC(hipMemcpyAsync(di, index, 8 * count, hipMemcpyHostToDevice, c.st));
+    HC(hipMemcpyAsync(dy, ys, 32 * count * l, hipMemcpyHostToDevice, c.st));
+    rc_run(c, b, nbits, lbits, di, dy, count, len, dc, de);
+    HC(hipMemcpyAsync(coef, dc, 32 * len, hipMemcpyDeviceToHost, c.st));
+    if (evals) HC(hipMemcpyAsync(evals, de, 32 * n, hipMemcpyDeviceToHost, c.st));
+  }
+  HC(hipMemcpyAsync(hf, b.flags, 16, hipMemcpyDeviceToHost, c.st));
+  c.sync();
+  uint32_t flags[4];
+  memcpy(flags, hf, 16);
+  c.reset_staging();
+  return rc_verdict(c, fn, flags, (const uint64_t*)index, device, nbits, lbits);
+  API_END
+}
+
+}  // namespace
+
+extern "C" {
+
+int kgs_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const uint64_t* index, const uint8_t* ys_mont,
+                           uint64_t count, uint64_t len, uint8_t* coef_mont, uint8_t* evals_mont) {
+  return recover_entry(ctx, nbits, lbits, index, ys_mont, count, len, coef_mont, evals_mont, false);
+}
+
+int kgs_kzg_recover_cosets_device(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                  uint64_t count, uint64_t len, void* d_coef_mont, void* d_evals_mont) {
+  return recover_entry(ctx, nbits, lbits, d_index, d_ys_mont, count, len, d_coef_mont, d_evals_mont, true);
+}
+
+// ---- timing helper of profiles/kzg_recover_cosets_time.py
+int kgs_bench_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
+                                 uint64_t count, uint64_t len, void* d_coef_mont, int what, int leaf_log, int reps,
+                                 double* ms) {
+  API_BEGIN
+  const char* fn = "kgs_bench_kzg_recover_cosets";
+  rc_check_args(ctx, fn, nbits, lbits, d_index, d_ys_mont, count, len, d_coef_mont);
+  if (!ms || what < 0 || what > 3 || reps < 1) throw KgsError(KGS_E_ARG, std::string(fn) + ": bad what / reps / ms");
+  if (!leaf_log) leaf_log = RC_LEAF_LOG;
+  if (leaf_log < RC_LEAF_LOG_MIN || leaf_log > RC_LEAF_LOG_MAX)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": leaf_log must be 0 or in " + std::to_string(RC_LEAF_LOG_MIN) + " .. " +
+                                  std::to_string(RC_LEAF_LOG_MAX));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  rc_check_ctx(*ctx, fn);
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  if (nbits > c.logM) ensure_domain(c, nbits);
+  const RcBufs b = rc_bufs(c, nbits, lbits);
+  const int logm = nbits - lbits;
+  // every leg after one whole call: the buffers grown and holding this input's intermediate values
+  rc_run(c, b, nbits, lbits, (const uint64_t*)d_index, (const uint32_t*)d_ys_mont, count, len, (uint32_t*)d_coef_mont, nullptr,
+         leaf_log);
+  HC(hipStreamSynchronize(c.st));
+  hipEvent_t e0, e1;
+  HC(hipEventCreate(&e0));
+  HC(hipEventCreate(&e1));
+  for (int r = 0; r < reps; r++) {
+    HC(hipEventRecord(e0, c.st));
+    if (what == 0)
+      rc_run(c, b, nbits, lbits, (const uint64_t*)d_index, (const uint32_t*)d_ys_mont, count, len, (uint32_t*)d_coef_mont,
+             nullptr, leaf_log);
+    else if (what == 1)
+      rc_tree(c, b, (const uint64_t*)d_index, count, logm, leaf_log);
+    else if (what == 2)
+      rc_mside(c, b, count, logm, lbits);
+    else
+      rc_nside(c, b, nbits, lbits, false);
+    HC(hipEventRecord(e1, c.st));
+    check_launch();
+    HC(hipEventSynchronize(e1));
+    float f = 0;
+    HC(hipEventElapsedTime(&f, e0, e1));
+    ms[r] = f;
+  }
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  c.reset_staging();
+  API_END
+}
+
+}  // extern "C"

@@ -850,6 +850,88 @@ void ntt_dit(hipStream_t st, uint32_t* out, const uint32_t* in, int in_bitrev, i
   }
 }
 
+// ---------------------------------------------------------------- batched transforms over contiguous blocks
+// The stage tables are indexed by stage (tw[h + t] = w_{2h}^t), not by transform size, and a butterfly's t is
+// its index masked by h - 1. So the 2^(logtotal - s) transforms of size 2^s over the consecutive blocks of an
+// array of 2^logtotal elements are the last s stages of that array's decimation-in-frequency transform, and
+// the first s stages of its decimation-in-time one: the same kernels with another (logm, s0). Routes, each a
+// pass shape the whole transforms already launch (a pass's group stride is 1 or at least a tile's run):
+//   s >= 11            the passes of lds_plan(s), as a transform of size 2^s takes them
+//   4 <= s <= 10       one LDS pass of min(s, 9) contiguous stages, and for s = 10 one radix-2 pass beside it
+//   s < 4 or an array below one tile   the radix-8/4/2 passes
+static void dif_radix(hipStream_t st, uint32_t* data, const uint32_t* tw, int logtotal, int s0, int s1) {
+  while (s0 < s1) {
+    const int K = s1 - s0 >= 3 ? 3 : s1 - s0;
+    const uint64_t groups = (1ull << logtotal) >> K;
+    if (K == 3)
+      hipLaunchKernelGGL(k_ntt_dif_pass<3>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 0, nullptr, tw, 0, logtotal, s0);
+    else if (K == 2)
+      hipLaunchKernelGGL(k_ntt_dif_pass<2>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 0, nullptr, tw, 0, logtotal, s0);
+    else
+      hipLaunchKernelGGL(k_ntt_dif_pass<1>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 0, nullptr, tw, 0, logtotal, s0);
+    s0 += K;
+  }
+}
+static void dit_radix(hipStream_t st, uint32_t* data, const uint32_t* tw, int logtotal, int s0, int s1,
+                      const uint32_t* post_s) {
+  while (s0 < s1) {
+    const int K = s1 - s0 >= 3 ? 3 : s1 - s0;
+    const uint64_t groups = (1ull << logtotal) >> K;
+    const uint32_t* ps = s0 + K == s1 ? post_s : nullptr;
+    if (K == 3)
+      hipLaunchKernelGGL(k_ntt_dit_pass<3>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 1, tw, 0, logtotal, s0, nullptr, ps);
+    else if (K == 2)
+      hipLaunchKernelGGL(k_ntt_dit_pass<2>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 1, tw, 0, logtotal, s0, nullptr, ps);
+    else
+      hipLaunchKernelGGL(k_ntt_dit_pass<1>, dim3(nblocks(groups)), dim3(256), 0, st, data, nullptr, 1, tw, 0, logtotal, s0, nullptr, ps);
+    s0 += K;
+  }
+}
+
+void ntt_dif_blocks(hipStream_t st, uint32_t* data, int logtotal, int s, const uint32_t* tw) {
+  if (s <= 0) return;
+  const int base = logtotal - s;
+#ifndef KGS_NO_NTT_LDS
+  if (logtotal >= LDS_MIN_LOGM && s >= LDS_MIN_LOGM) {
+    int ks[8];
+    const int P = lds_plan(s, ks);
+    for (int i = 0, s0 = base; i < P; s0 += ks[i++])
+      launch_lds_pass(st, ks[i], false, data, nullptr, 0, 1, nullptr, tw, logtotal, s0, nullptr, nullptr);
+    return;
+  }
+  if (logtotal >= LDS_MIN_LOGM && s >= 4) {
+    const int K = s < LDS_MAX_K ? s : LDS_MAX_K;
+    dif_radix(st, data, tw, logtotal, base, logtotal - K);
+    launch_lds_pass(st, K, false, data, nullptr, 0, 1, nullptr, tw, logtotal, logtotal - K, nullptr, nullptr);
+    return;
+  }
+#endif
+  dif_radix(st, data, tw, logtotal, base, logtotal);
+}
+
+void ntt_dit_blocks(hipStream_t st, uint32_t* data, int logtotal, int s, const uint32_t* tw, const uint32_t* post_s) {
+  if (s <= 0) return;
+#ifndef KGS_NO_NTT_LDS
+  if (logtotal >= LDS_MIN_LOGM && s >= LDS_MIN_LOGM) {
+    int ks[8];
+    const int P = lds_plan(s, ks);
+    for (int i = 0, s0 = 0; i < P; i++) {
+      const int K = ks[P - 1 - i];
+      launch_lds_pass(st, K, true, data, nullptr, 0, 1, nullptr, tw, logtotal, s0, nullptr, i == P - 1 ? post_s : nullptr);
+      s0 += K;
+    }
+    return;
+  }
+  if (logtotal >= LDS_MIN_LOGM && s >= 4) {
+    const int K = s < LDS_MAX_K ? s : LDS_MAX_K;
+    launch_lds_pass(st, K, true, data, nullptr, 0, 1, nullptr, tw, logtotal, 0, nullptr, K == s ? post_s : nullptr);
+    dit_radix(st, data, tw, logtotal, K, s, post_s);
+    return;
+  }
+#endif
+  dit_radix(st, data, tw, logtotal, 0, s, post_s);
+}
+
 // tw[j] = w^j for j < count, computed in chunks of 64 from w^(64 t) by square-and-multiply.
 __global__ void k_powers(uint32_t* __restrict__ out, uint64_t count, const uint32_t* __restrict__ wp,
                          const uint32_t* __restrict__ scale) {

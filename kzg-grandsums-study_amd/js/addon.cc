@@ -305,6 +305,7 @@ struct Job {
                // 10 = every opening of a polynomial on its domain (kzgOpenAll)
                // 11 = every coset opening of a polynomial (kzgOpenCosets)
                // 12 = a batch of coset openings against one SRS (kzgVerifyCosetsBatch)
+               // 13 = a polynomial back from a subset of its cosets (kzgRecoverCosets)
   int rc = 0;
   std::string err;
   // load
@@ -342,6 +343,10 @@ struct Job {
   std::vector<uint64_t> cb_index;
   std::vector<uint8_t> cb_ys, cb_proofs, cb_seed;
   kgs_coset_batch_diag_t cb_diag = {};
+  // kzgRecoverCosets: ntt_logm / ntt_inverse = nBits / lBits; the coset indices in cb_index, the values in cb_ys
+  // (copied), the length in rc_len; the coefficients come back in `scal`, the evaluations in `ev`, the verdict in rc_ok
+  uint64_t rc_len = 0;
+  int rc_ok = 0;
   // proveMulti: the arguments' kinds and borrowed input views
   struct MultiArg {
     int kind = 0;
@@ -540,6 +545,13 @@ static void job_execute(napi_env, void* data) {
                                                j->cb_seed.empty() ? nullptr : j->cb_seed.data(), j->vb_valid.data(),
                                                &j->cb_diag);
     j->rc = rc < 0 ? rc : KGS_OK;
+  } else if (j->op == 13) {
+    j->scal.resize(32 * (size_t)j->rc_len);
+    j->ev.resize((size_t)32 << j->ntt_logm);
+    const int rc = kgs_kzg_recover_cosets(j->ctx, j->ntt_logm, j->ntt_inverse, j->cb_index.data(), j->cb_ys.data(),
+                                          j->cb_index.size(), j->rc_len, j->scal.data(), j->ev.data());
+    j->rc_ok = rc == 1;
+    j->rc = rc < 0 ? rc : KGS_OK;
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -576,6 +588,14 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_value o;
     napi_create_object(env, &o);
     napi_set_named_property(env, o, "proofs", make_u8(env, j->bases.data(), j->bases.size()));
+    napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
+    napi_resolve_deferred(env, j->deferred, o);
+  } else if (j->op == 13) {
+    napi_value o, v;
+    napi_create_object(env, &o);
+    napi_get_boolean(env, j->rc_ok != 0, &v);
+    napi_set_named_property(env, o, "ok", v);
+    napi_set_named_property(env, o, "coefs", make_u8(env, j->scal.data(), j->scal.size()));
     napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
     napi_resolve_deferred(env, j->deferred, o);
   } else if (j->op == 12) {
@@ -1288,6 +1308,45 @@ static napi_value KzgVerifyCosetsBatch(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_kzg_verify_cosets_batch");
 }
 
+// kzgRecoverCosets(ctx, nBits, lBits, index, ysMont, length) -> Promise<{ok, coefs, evals}> (kgs_kzg_recover_cosets):
+// index an array of count distinct coset indices, ysMont count * 2^lBits x 32 B Montgomery values (row k = the values
+// on coset index[k]), length the number of coefficients (count * 2^lBits >= length); coefs length x 32 B, evals
+// 2^nBits x 32 B, both meaningless when ok is false
+static napi_value KzgRecoverCosets(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 13;
+  j->ctx = get_ctx(env, argv[0]);
+  int32_t nbits = -1, lbits = -1;
+  int64_t len = -1;
+  napi_get_value_int32(env, argv[1], &nbits);
+  napi_get_value_int32(env, argv[2], &lbits);
+  uint32_t ni = 0;
+  napi_get_array_length(env, argv[3], &ni);
+  bool ok = nbits >= 0 && nbits <= 23 && lbits >= 0 && lbits <= nbits;
+  for (uint32_t k = 0; ok && k < ni; k++) {
+    napi_value v;
+    int64_t i = -1;
+    napi_get_element(env, argv[3], k, &v);
+    napi_get_value_int64(env, v, &i);
+    ok = i >= 0;
+    j->cb_index.push_back((uint64_t)i);
+  }
+  j->cb_ys = bytes_of(env, argv[4]);
+  napi_get_value_int64(env, argv[5], &len);
+  if (!ok || ni < 1 || len < 1 || len > ((int64_t)1 << nbits) || j->cb_ys.size() != ((size_t)32 * ni << lbits)) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgRecoverCosets: expected nBits <= 23, lBits <= nBits, count >= 1 coset indices, count * 2^lBits x 32 B values, 1 <= length <= 2^nBits");
+    return nullptr;
+  }
+  j->ntt_logm = nbits;
+  j->ntt_inverse = lbits;
+  j->rc_len = (uint64_t)len;
+  return queue(env, j, "kgs_kzg_recover_cosets");
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1327,6 +1386,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"kzgOpenCosets", nullptr, KzgOpenCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCoset", nullptr, KzgVerifyCoset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCosetsBatch", nullptr, KzgVerifyCosetsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgRecoverCosets", nullptr, KzgRecoverCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

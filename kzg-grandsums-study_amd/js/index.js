@@ -29,6 +29,9 @@ module.exports = {
     // many coset openings {commit, index, ys, proof} against one SRS with one pairing check, folded on the GPU
     // (kgs_kzg_verify_cosets_batch)
     kzg_verify_cosets_batch: require("./src/backend").kzgVerifyCosetsBatch,
+    // kzg_recover_cosets(nBits, lBits, cells, length) -> Promise<{ok, coefs, evals}>: the polynomial of `length`
+    // coefficients through the cells {index, ys} it is given, rebuilt on the GPU (kgs_kzg_recover_cosets)
+    kzg_recover_cosets: require("./src/backend").kzgRecoverCosets,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

@@ -284,6 +284,17 @@ async function kzgVerifyCosetsBatch(commits, nBits, lBits, openings, srsG1, tauL
     return Object.assign(res, { valid });
 }
 
+// A polynomial of `length` coefficients back from a subset of its cosets (kgs_kzg_recover_cosets; needs no SRS)
+// -> Promise<{ok, coefs: length x 32 B Montgomery, evals: 2^nBits x 32 B Montgomery}>. cells: an array of {index (the
+// coset, < 2^(nBits - lBits), each at most once), ys (its 2^lBits values p(w^(index + 2^(nBits - lBits) j)), 32 B
+// Montgomery each)}, in any order, with cells.length * 2^lBits >= length. ok is false when the values lie on no
+// polynomial of degree < length; coefs and evals mean nothing then.
+async function kzgRecoverCosets(nBits, lBits, cells, length) {
+    const ys = Buffer.concat(cells.map(c => Buffer.from(contiguous(c.ys))));
+    return withContext(slot => load().kzgRecoverCosets(slot.ctx, nBits, lBits, cells.map(c => c.index),
+        new Uint8Array(ys), length));
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -336,4 +347,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, kzgVerifyCosetsBatch, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, kzgVerifyCosetsBatch, kzgRecoverCosets, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
