@@ -706,6 +706,31 @@ int kgs_kzg_open_cosets_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t
 /* 1 when the SRS side of kgs_kzg_open_cosets for (nbits, lbits) is cached on the device for ctx's SRS (lbits
  * = 0: kgs_kzg_open_all's row), else 0: such a call builds nothing. No GPU work. */
 int kgs_kzg_open_cosets_cached(kgs_ctx_t* ctx, int nbits, int lbits);
+/* kgs_kzg_open_cosets for `polys` polynomials over one (nbits, lbits) and one SRS, every stage launched once for
+ * the whole set: one layout kernel and one batched Fr transform for the polys * l coefficient rows,
+ * one multiply-sum pass of polys * 2n terms against the l cached rows, and the two G1 transforms as batched
+ * stages that give a wave one twiddle across polynomials and groups. A transform of 128 points costs a single
+ * call as much time as one of thousands; here the polynomials share those stages.
+ *   coef_mont   polynomial b has its len <= 2^nbits Montgomery coefficients at coef_mont + 32 * stride * b;
+ *               stride >= len, and what lies between len and stride is not read
+ *   polys       polys * 2^nbits <= 2^24; polys == 0 does nothing and returns KGS_OK
+ *   nbits, lbits  as for kgs_kzg_open_cosets
+ *   proofs_lem  polys * 2^(nbits - lbits) canonical affine LEM points, polynomial after polynomial
+ *   evals_mont  NULL, or polys * 2^nbits x 32 B, polynomial after polynomial, each in natural order
+ * Results: the bytes kgs_kzg_open_cosets gives for polynomial b alone, at every lbits 0 .. nbits, for len == 0 and
+ * for one coset (lbits == nbits). lbits == 0 runs kgs_kzg_open_all's path polynomial after polynomial: it has no
+ * rows to share a multiply-sum pass over. The SRS side is kgs_kzg_open_cosets' cached row of (SRS, nbits, lbits):
+ * either call builds it for the other, and kgs_kzg_open_cosets_cached reports it.
+ * Failures: KGS_E_SRS "no SRS loaded"; KGS_E_ARG (the message names the offender) for a NULL ctx, a NULL buffer
+ * with work to do, stride < len, len > 2^nbits, polys * 2^nbits > 2^24, nbits or lbits out of range, a rank group,
+ * MSM sharding, an SRS slice. Context contract as for kgs_kzg_open_cosets: device buffers of the call's own
+ * ("km_*", about 450 B per coefficient slot polys * 2^nbits), nothing of the prover's, of the window tables or of
+ * the other caches touched, idle on return, on error paths too. */
+int kgs_kzg_open_cosets_many(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t polys, uint64_t stride, uint64_t len,
+                             int nbits, int lbits, uint8_t* proofs_lem, uint8_t* evals_mont);
+/* Same with device pointers (on ctx's device); d_coef_mont is only read. */
+int kgs_kzg_open_cosets_many_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t polys, uint64_t stride,
+                                    uint64_t len, int nbits, int lbits, void* d_proofs_lem, void* d_evals_mont);
 /* Host only (no GPU, no context): the check of one coset opening of kgs_kzg_open_cosets,
  * e(-proof, [tau^l]_2) e(C - [I(tau)]_1 + a_i proof, [1]_2) == 1, where I interpolates the l values
  * ys_mont[j] = p(w^(index + m j)): I = sum_k d_k X^k with d_k = w^(-index k) J_k and J the inverse transform
@@ -866,6 +891,14 @@ int kgs_bench_kzg_open_all(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len
  * sums: the other arm of the A/B of DESIGN.md §20; what 2 runs the pass as it ships, two rows per lane). */
 int kgs_bench_kzg_open_cosets(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t len, int nbits, int lbits, int what,
                               int reps, double* ms);
+/* `reps` runs of a leg of kgs_kzg_open_cosets_many_device (1 <= lbits < nbits, 1 <= len <= stride, polys >= 1), as
+ * kgs_bench_kzg_open_cosets times its own: after one whole call, each between two events on ctx's stream. what:
+ * 0 the call with the cache warm, 1 the Fr side (layout, batched transform, bit reversal), 2 the multiply-sum pass
+ * and its affine conversion, 3 the two batched G1 transforms and the slice between them, 4 the same with the
+ * per-lane mapping forced in every stage (the other arm of the A/B of DESIGN.md §23), 5 the yardstick: polys runs
+ * of kgs_kzg_open_cosets_device's work, one polynomial after the other, enqueued back to back. */
+int kgs_bench_kzg_open_cosets_many(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t polys, uint64_t stride, uint64_t len,
+                                   int nbits, int lbits, int what, int reps, double* ms);
 /* The route kgs_commit_evals_device replaces, with the same device-resident input: to Montgomery form,
  * inverse NTT, kgs_msm over the resident window tables (profiles/g1_ntt_time.py times both by the wall
  * clock; each ends synchronised). */

@@ -199,6 +199,14 @@ def lib():
         L.kgs_kzg_open_cosets_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_kzg_open_cosets_cached.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.kgs_kzg_open_cosets_many.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_int, ctypes.c_int, c_u8p, c_u8p]
+        L.kgs_kzg_open_cosets_many_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                      ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                      ctypes.c_void_p]
+        L.kgs_bench_kzg_open_cosets_many.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                     ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         L.kgs_kzg_verify_coset.argtypes = [c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, c_u8p, c_u8p, c_u8p,
                                            c_u8p]
         L.kgs_kzg_verify_cosets_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_u8p, ctypes.c_uint64,
@@ -881,6 +889,36 @@ class Context:
         Montgomery coefficients, read only; d_proofs to 2^(nbits - lbits) x 64 writable bytes; d_evals to
         2^nbits x 32 writable bytes, or None."""
         _check(lib().kgs_kzg_open_cosets_device(self._h, d_coef, n, nbits, lbits, d_proofs, d_evals))
+
+    def kzg_open_cosets_many(self, coefs, nbits, lbits, evals=False):
+        """kzg_open_cosets for many polynomials over one (nbits, lbits) in one call (kgs_kzg_open_cosets_many): every
+        stage runs once for the whole set, so small polynomials share the latency a single call pays alone. coefs:
+        a list of bytes-likes of Montgomery coefficients, at most 2^nbits of 32 B each; unequal lengths are
+        zero-padded to the longest, which changes no proof. len(coefs) * 2^nbits is at most 2^24. Returns the list
+        of the proofs kzg_open_cosets gives for each polynomial, byte for byte, or with evals=True the pair (list
+        of proofs, list of evaluations)."""
+        coefs = [bytes(c) for c in coefs]
+        if any(len(c) % 32 for c in coefs):
+            raise ValueError("coefs must hold 32-byte elements")
+        polys = len(coefs)
+        n = max((len(c) // 32 for c in coefs), default=0)
+        packed = b"".join(c + bytes(32 * n - len(c)) for c in coefs)
+        ok = 0 <= nbits <= 23 and 0 <= lbits <= nbits  # else the library refuses before it writes
+        psz, esz = (64 << (nbits - lbits), 32 << nbits) if ok else (64, 32)
+        proofs = ctypes.create_string_buffer(max(psz * polys, 1))
+        ev = ctypes.create_string_buffer(max(esz * polys, 1)) if evals else None
+        pc, kc = _ptr(packed) if packed else (None, None)  # read in place
+        _check(lib().kgs_kzg_open_cosets_many(self._h, pc, polys, n, n, nbits, lbits, proofs, ev))
+        del kc
+        out = [proofs.raw[psz * b:psz * (b + 1)] for b in range(polys)]
+        return (out, [ev.raw[esz * b:esz * (b + 1)] for b in range(polys)]) if evals else out
+
+    def kzg_open_cosets_many_device(self, d_coef, polys, stride, n, nbits, lbits, d_proofs, d_evals=None):
+        """Device-resident twin (kgs_kzg_open_cosets_many_device): d_coef is a device pointer (int), read only,
+        polynomial b's n <= 2^nbits Montgomery coefficients at d_coef + 32 * stride * b (stride >= n; the gap is
+        not read); d_proofs to polys * 2^(nbits - lbits) x 64 writable bytes; d_evals to polys * 2^nbits x 32
+        writable bytes, or None."""
+        _check(lib().kgs_kzg_open_cosets_many_device(self._h, d_coef, polys, stride, n, nbits, lbits, d_proofs, d_evals))
 
     def kzg_verify_cosets_batch(self, tau_l_g2, srs_g1, nbits, lbits, commits, openings, locate=True, seed=None,
                                 diag=None):
@@ -1588,6 +1626,21 @@ def kzg_open_cosets(pTauFilename, coefs, lbits, device=0):
     ctx = _context(device)
     ctx.load_ptau(pTauFilename, nbits)
     return ctx.kzg_open_cosets(coefs, nbits, lbits, evals=True)
+
+
+def kzg_open_cosets_many(pTauFilename, coefs, lbits, device=0):
+    """Every coset opening of each polynomial of the list `coefs` (bytes-likes of Montgomery coefficients) on the
+    smallest domain 2^nbits that holds the longest of them and 2^lbits points, over the SRS of pTauFilename, in one
+    call (kgs_kzg_open_cosets_many): returns (list of proofs, list of evaluations), each entry what kzg_open_cosets
+    returns for that polynomial on that domain."""
+    coefs = [bytes(c) for c in coefs]
+    if any(len(c) % 32 for c in coefs):
+        raise ValueError("coefs must hold 32-byte elements")
+    longest = max((len(c) // 32 for c in coefs), default=0)
+    nbits = max(max(longest - 1, 0).bit_length(), lbits)
+    ctx = _context(device)
+    ctx.load_ptau(pTauFilename, nbits)
+    return ctx.kzg_open_cosets_many(coefs, nbits, lbits, evals=True)
 
 
 def ptau_read_tau_g2_pow(pTauFilename, k):

@@ -3,6 +3,10 @@
 // Lagrange-basis SRS of the resident SRS) and kgs_commit_evals / kgs_commit_evals_device (a commitment
 // straight from evaluations, over those bases).
 //
+// Further down: the openings over the whole resident SRS, kgs_kzg_open_all (§19), kgs_kzg_open_cosets (§20) and
+// kgs_kzg_open_cosets_many (§23: §20's pipeline with a polynomial dimension in every stage), with their caches
+// and timing helpers.
+//
 // Host: argument checks, the root and the scaling constant, the call's own device buffers ("gn_*" in the
 // context's pool, grown on demand, g1_ntt_sizes), the per-device cache of Lagrange rows on the SrsTables
 // entry, and for ctx == NULL the transform itself with the host curve code. Nothing of the prover's
@@ -454,6 +458,152 @@ int kzg_open_cosets_entry(kgs_ctx_t* ctx, const void* coef, uint64_t len, int nb
   API_END
 }
 
+// ------------------------------------------------------------------ coset openings of many polynomials
+constexpr uint64_t KZG_MANY_MAX_SLOTS = 1ull << 24;  // polys * n
+
+int log2_ceil(uint64_t x) {
+  int lg = 0;
+  while ((1ull << lg) < x) lg++;
+  return lg;
+}
+
+// The sizes and the device buffers of one call ("km_*": the call's own, beside the single call's "fk_*" / "gn_*").
+// lbits >= 1 here; lbits = 0 goes polynomial by polynomial through kzg_open_all_run.
+struct CosetsMany {
+  uint64_t polys, stride, len, n, l, m;
+  int nbits, lbits, logm;
+  int log_fr_blocks;  // the l polys blocks of 2m of the Fr side, rounded up to the power of two ntt_dif_blocks takes
+  int log_ev_blocks;  // the polys blocks of n of the evaluations, likewise
+  uint32_t *fr = nullptr, *chat = nullptr, *h = nullptr;
+  G1NttWork w;  // xyzz: the products of the multiply-sum pass, then the stages' outputs; aff: u, in place
+};
+
+CosetsMany cosets_many_plan(kgs_ctx& c, uint64_t polys, uint64_t stride, uint64_t len, int nbits, int lbits) {
+  CosetsMany q;
+  q.polys = polys, q.stride = stride, q.len = len, q.nbits = nbits, q.lbits = lbits, q.logm = nbits - lbits;
+  q.n = 1ull << nbits, q.l = 1ull << lbits, q.m = q.n >> lbits;
+  q.log_fr_blocks = log2_ceil(q.l * polys);
+  q.log_ev_blocks = log2_ceil(polys);
+  const uint64_t fr_elems = std::max((2 * q.m) << q.log_fr_blocks, q.n << q.log_ev_blocks);
+  const uint64_t terms = 2 * q.n * polys, upts = 2 * q.m * polys;
+  q.fr = c.buf("km_fr", 32 * fr_elems);
+  q.chat = c.buf("km_chat", 32 * terms);
+  q.h = c.buf("km_h", 64 * q.m * polys);
+  // two rows per lane leave l / 2 rows of products (launch_g1_mul_sum), one row per lane all l; l >= 2
+  q.w.xyzz = c.buf("km_xyzz", 128 * (terms >= G1_MUL_GROUP_MIN_TERMS ? terms / 2 : terms));
+  q.w.aff = c.buf("km_aff", 64 * upts);
+  q.w.scratch = c.buf("km_scratch", 32 * upts);
+  q.w.tw = c.buf("km_tw", 4 * (uint64_t)G1NTT_TW_WORDS * (q.m + 1));
+  return q;
+}
+
+// c^: the l polys zero-padded Fr transforms of size 2m, natural order, rows over polynomials, into q.chat
+void cosets_many_fr(kgs_ctx& c, const CosetsMany& q, const uint32_t* d_coef) {
+  launch_coset_rows_many(c.st, q.fr, d_coef, q.polys, q.stride, q.len, q.logm, q.lbits, q.logm + 1, 1ull << q.log_fr_blocks);
+  ntt_dif_blocks(c.st, q.fr, q.log_fr_blocks + q.logm + 1, q.logm + 1, c.tw_fwd);
+  launch_bitrev_blocks(c.st, q.chat, q.fr, q.logm + 1, q.l * q.polys);
+}
+
+// u^[p][i] = sum_r c^[r][p][i] x (the cached points)[r][i], affine, into q.w.aff
+void cosets_many_pointwise(kgs_ctx& c, const CosetsMany& q, const FkRow& row) {
+  launch_g1_mul_sum_many(c.st, q.w.xyzz, row.xhat, q.chat, q.l, q.polys, 2 * q.m);
+  launch_batch_affine(c.st, q.w.aff, q.w.xyzz, q.w.scratch, 2 * q.m * q.polys);
+}
+
+// coset_transforms for all the polynomials: the unscaled inverses of size 2m in place in q.w.aff, the slices, the
+// forward transforms of size m into d_proofs
+void cosets_many_transforms(kgs_ctx& c, const CosetsMany& q, uint32_t* d_proofs, int mapping) {
+  uint32_t root[8];
+  fr_words(ntt_root(q.logm + 1, true), root);
+  g1_ntt_many_run(c.st, q.w, q.w.aff, q.w.aff, q.polys, q.logm + 1, root, mapping);
+  launch_coset_slice_many(c.st, q.h, q.w.aff, q.logm, q.polys);
+  fr_words(ntt_root(q.logm, false), root);
+  g1_ntt_many_run(c.st, q.w, d_proofs, q.h, q.polys, q.logm, root, mapping);
+}
+
+// kgs_kzg_open_cosets_many on the main stream (not synchronised): the coset openings of the `polys` polynomials
+// at d_coef (device; polynomial p at d_coef + 8 stride p words) into d_proofs (polys x m points) and d_evals
+// (polys x n elements, or nullptr). The caller holds the context, has checked it and reset its staging.
+void kzg_open_cosets_many_run(kgs_ctx& c, const uint32_t* d_coef, uint64_t polys, uint64_t stride, uint64_t len, int nbits,
+                              int lbits, uint32_t* d_proofs, uint32_t* d_evals) {
+  const uint64_t n = 1ull << nbits, m = n >> lbits;
+  if (!lbits) {  // one coset per point: no rows to sum over, kgs_kzg_open_all's path polynomial after polynomial
+    for (uint64_t p = 0; p < polys; p++)
+      kzg_open_all_run(c, d_coef + 8 * stride * p, len, nbits, d_proofs + 16 * n * p, d_evals ? d_evals + 8 * n * p : nullptr);
+    return;
+  }
+  if (!len) {  // zero polynomials
+    HC(hipMemsetAsync(d_proofs, 0, 64 * m * polys, c.st));
+    if (d_evals) HC(hipMemsetAsync(d_evals, 0, 32 * n * polys, c.st));
+    return;
+  }
+  std::shared_ptr<FkRow> row;
+  if (m > 1) row = coset_row(c, nbits, lbits);
+  if (c.logM < (d_evals ? nbits : nbits - lbits + 1)) ensure_domain(c, d_evals ? nbits : nbits - lbits + 1);
+  const CosetsMany q = cosets_many_plan(c, polys, stride, len, nbits, lbits);
+  if (m == 1) {  // one coset, the whole domain: p = I, the quotient is zero
+    HC(hipMemsetAsync(d_proofs, 0, 64 * polys, c.st));
+  } else {
+    cosets_many_fr(c, q, d_coef);
+    cosets_many_pointwise(c, q, *row);
+    cosets_many_transforms(c, q, d_proofs, G1NTT_MAP_AUTO);
+  }
+  if (d_evals) {  // the polys transforms of size n of the zero-padded coefficients, natural order
+    launch_coset_rows_many(c.st, q.fr, d_coef, polys, stride, len, nbits, 0, nbits, 1ull << q.log_ev_blocks);
+    ntt_dif_blocks(c.st, q.fr, q.log_ev_blocks + nbits, nbits, c.tw_fwd);
+    launch_bitrev_blocks(c.st, d_evals, q.fr, nbits, polys);
+  }
+  check_launch();
+}
+
+// the refusals of kgs_kzg_open_cosets_many beyond a NULL context (the caller holds the context)
+void check_cosets_many(const kgs_ctx& c, uint64_t polys, uint64_t stride, uint64_t len, int nbits, int lbits, const char* fn) {
+  check_open_all(c, nbits, fn);
+  if (lbits < 0 || lbits > nbits)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": lbits must be in 0 .. nbits = " + std::to_string(nbits));
+  const uint64_t n = 1ull << nbits;
+  if (len > n)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": len = " + std::to_string(len) + " coefficients do not fit the domain of 2^" +
+                                  std::to_string(nbits) + " points.");
+  if (stride < len)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": stride = " + std::to_string(stride) + " is below len = " + std::to_string(len));
+  if (polys > KZG_MANY_MAX_SLOTS >> nbits)
+    throw KgsError(KGS_E_ARG, std::string(fn) + ": polys = " + std::to_string(polys) + " times 2^nbits is above 2^24.");
+}
+
+int kzg_open_cosets_many_entry(kgs_ctx_t* ctx, const void* coef, uint64_t polys, uint64_t stride, uint64_t len, int nbits,
+                               int lbits, void* proofs, void* evals, bool device) {
+  API_BEGIN
+  const char* fn = "kgs_kzg_open_cosets_many";
+  if (!ctx) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL ctx");
+  if (!polys) return KGS_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_cosets_many(*ctx, polys, stride, len, nbits, lbits, fn);
+  if (!proofs) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL proofs buffer");
+  if (len && !coef) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL coefficient buffer");
+  const uint64_t n = 1ull << nbits, m = n >> lbits;
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  if (device) {
+    kzg_open_cosets_many_run(c, (const uint32_t*)coef, polys, stride, len, nbits, lbits, (uint32_t*)proofs, (uint32_t*)evals);
+  } else {
+    uint32_t* dc = c.buf("km_coef", 32 * (len ? len * polys : 1));  // packed: the gaps stay on the host
+    uint32_t* dp = c.buf("km_out", 64 * m * polys);
+    uint32_t* de = evals ? c.buf("km_ev", 32 * n * polys) : nullptr;
+    if (len && stride == len)
+      HC(hipMemcpyAsync(dc, coef, 32 * len * polys, hipMemcpyHostToDevice, c.st));
+    else if (len)
+      HC(hipMemcpy2DAsync(dc, 32 * len, coef, 32 * stride, 32 * len, polys, hipMemcpyHostToDevice, c.st));
+    kzg_open_cosets_many_run(c, dc, polys, len, len, nbits, lbits, dp, de);
+    HC(hipMemcpyAsync(proofs, dp, 64 * m * polys, hipMemcpyDeviceToHost, c.st));
+    if (evals) HC(hipMemcpyAsync(evals, de, 32 * n * polys, hipMemcpyDeviceToHost, c.st));
+  }
+  c.reset_staging();
+  API_END
+}
+
 int g1_mul_sum_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, uint64_t rows, uint64_t cols, void* out,
                      bool device) {
   API_BEGIN
@@ -633,6 +783,16 @@ int kgs_kzg_open_cosets_cached(kgs_ctx_t* ctx, int nbits, int lbits) {
   API_END
 }
 
+int kgs_kzg_open_cosets_many(kgs_ctx_t* ctx, const uint8_t* coef_mont, uint64_t polys, uint64_t stride, uint64_t len,
+                             int nbits, int lbits, uint8_t* proofs_lem, uint8_t* evals_mont) {
+  return kzg_open_cosets_many_entry(ctx, coef_mont, polys, stride, len, nbits, lbits, proofs_lem, evals_mont, false);
+}
+
+int kgs_kzg_open_cosets_many_device(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t polys, uint64_t stride,
+                                    uint64_t len, int nbits, int lbits, void* d_proofs_lem, void* d_evals_mont) {
+  return kzg_open_cosets_many_entry(ctx, d_coef_mont, polys, stride, len, nbits, lbits, d_proofs_lem, d_evals_mont, true);
+}
+
 int kgs_g1_mul_sum(kgs_ctx_t* ctx, const uint8_t* points_lem, const uint8_t* scalars_std, uint64_t rows, uint64_t cols,
                    uint8_t* out_lem) {
   return g1_mul_sum_entry(ctx, points_lem, scalars_std, rows, cols, out_lem, false);
@@ -807,6 +967,59 @@ int kgs_bench_kzg_open_cosets(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t 
       launch_g1_mul_each(c.st, w.xyzz, row->xhat, chat, 2 * n, false);
     else
       coset_pointwise(c, w, *row, chat, lbits, 1);
+    HC(hipEventRecord(e1, c.st));
+    check_launch();
+    HC(hipEventSynchronize(e1));
+    float f = 0;
+    HC(hipEventElapsedTime(&f, e0, e1));
+    ms[r] = f;
+  }
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  c.reset_staging();
+  API_END
+}
+
+// ---- timing helper of profiles/kzg_open_cosets_many_time.py
+int kgs_bench_kzg_open_cosets_many(kgs_ctx_t* ctx, const void* d_coef_mont, uint64_t polys, uint64_t stride, uint64_t len,
+                                   int nbits, int lbits, int what, int reps, double* ms) {
+  API_BEGIN
+  const char* fn = "kgs_bench_kzg_open_cosets_many";
+  if (!ctx || !d_coef_mont || !ms) throw KgsError(KGS_E_ARG, std::string(fn) + ": NULL argument");
+  if (what < 0 || what > 5 || reps < 1 || !polys) throw KgsError(KGS_E_ARG, std::string(fn) + ": bad what / reps / polys");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  check_cosets_many(*ctx, polys, stride, len, nbits, lbits, fn);
+  if (lbits < 1 || lbits >= nbits) throw KgsError(KGS_E_ARG, std::string(fn) + ": lbits must be in 1 .. nbits - 1");
+  if (len < 1) throw KgsError(KGS_E_ARG, std::string(fn) + ": len must be in 1 .. 2^nbits");
+  const uint64_t m = 1ull << (nbits - lbits);
+  HC(hipSetDevice(ctx->device));
+  kgs_ctx& c = *ctx;
+  DrainOnError drain(&c);
+  c.reset_staging();
+  const uint32_t* coef = (const uint32_t*)d_coef_mont;
+  uint32_t* out = c.buf("km_out", 64 * m * polys);
+  uint32_t* one = c.buf("fk_out", 64 * m);
+  // every leg after one whole call of each kind: the rows cached, the buffers grown, c^ in "km_chat", u in "km_aff"
+  kzg_open_cosets_run(c, coef, len, nbits, lbits, one, nullptr);
+  kzg_open_cosets_many_run(c, coef, polys, stride, len, nbits, lbits, out, nullptr);
+  HC(hipStreamSynchronize(c.st));
+  const std::shared_ptr<FkRow> row = coset_row(c, nbits, lbits);
+  const CosetsMany q = cosets_many_plan(c, polys, stride, len, nbits, lbits);
+  hipEvent_t e0, e1;
+  HC(hipEventCreate(&e0));
+  HC(hipEventCreate(&e1));
+  for (int r = 0; r < reps; r++) {
+    HC(hipEventRecord(e0, c.st));
+    if (what == 0)
+      kzg_open_cosets_many_run(c, coef, polys, stride, len, nbits, lbits, out, nullptr);
+    else if (what == 1)
+      cosets_many_fr(c, q, coef);
+    else if (what == 2)
+      cosets_many_pointwise(c, q, *row);
+    else if (what == 3 || what == 4)
+      cosets_many_transforms(c, q, out, what == 3 ? G1NTT_MAP_AUTO : G1NTT_MAP_LANE);
+    else
+      for (uint64_t p = 0; p < polys; p++) kzg_open_cosets_run(c, coef + 8 * stride * p, len, nbits, lbits, one, nullptr);
     HC(hipEventRecord(e1, c.st));
     check_launch();
     HC(hipEventSynchronize(e1));

@@ -21,7 +21,11 @@
 //     scalar registers and the schedule is uniform, as k_tab_scale's is for rho (msm.hip).
 //   * The inverse transform's 1/n (kgs_srs_lagrange: 2^256 / n, which also takes rho = 2^-256 off the
 //     table row) is one more multiplication per point by a launch-uniform constant, k_g1ntt_scale.
+//   * Many transforms of one size side by side (kgs_kzg_open_cosets_many): k_g1ntt_stage_many runs
+//     a stage of all of them in one launch; a wave then shares t across polynomials and groups (g1ntt_map.hpp), so
+//     a small transform, whose stages have fewer than 64 groups, still gets a wave-uniform record.
 #include "kernels.hpp"
+#include "g1ntt_map.hpp"
 
 namespace kgs {
 
@@ -141,6 +145,37 @@ __global__ void __launch_bounds__(64) k_g1ntt_stage(uint32_t* __restrict__ out_x
   U.store(out_xyzz + 32 * pb);
 }
 
+// One stage of `polys` transforms of size 2^logn side by side, transform p over the points
+// [p n, (p + 1) n) of in_aff / out_xyzz, all with the one twiddle table of their size. The butterfly is
+// k_g1ntt_stage's; the lanes come from g1ntt_map.hpp. UNI: a block's 64 lanes share t across polynomials and
+// groups (polys * G >= 64), the record is wave-uniform whatever G is. Grid: g1ntt_many_blocks.
+template <bool UNI>
+__global__ void __launch_bounds__(64) k_g1ntt_stage_many(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
+                                                         const uint32_t* __restrict__ tw, uint64_t polys, int logh, int logn,
+                                                         int bitrev_in) {
+  KGS_AUX_PRIO();
+  const G1NttBfly m = g1ntt_many_map(blockIdx.x, threadIdx.x, polys, logn, logh, UNI);
+  if (!m.active) return;
+  uint64_t sa = m.pa, sb = m.pb;
+  if (bitrev_in) {  // within the polynomial's own block
+    const uint64_t base = m.poly << logn;
+    sa = base + (__brev((uint32_t)(m.pa - base)) >> (32 - logn));
+    sb = base + (__brev((uint32_t)(m.pb - base)) >> (32 - logn));
+  }
+  const g1_aff a = g1_aff::load(in_aff + 16 * sa), b = g1_aff::load(in_aff + 16 * sb);
+  g1_xyzz T;
+  if (m.t == 0)
+    T = g1_xyzz::from_aff(b);
+  else
+    T = g1ntt_mul<UNI>(b, tw + G1NTT_TW_WORDS * m.tw);
+  g1_xyzz U = T;
+  U.Y = U.Y.neg();
+  T.add_aff(a);
+  U.add_aff(a);
+  T.store(out_xyzz + 32 * m.pa);
+  U.store(out_xyzz + 32 * m.pb);
+}
+
 // out_xyzz[i] = k * in_aff[i] for the one record at rec
 __global__ void __launch_bounds__(64) k_g1ntt_scale(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
                                                     const uint32_t* __restrict__ rec, uint64_t n) {
@@ -160,12 +195,20 @@ __global__ void __launch_bounds__(64) k_g1ntt_scale(uint32_t* __restrict__ out_x
 // against 254 * 9 + 85 * 10, a factor 1.54 (measured 1.57 at 2^21 points). The record in
 // LDS instead (120 VGPRs, four waves per SIMD instead of three) measured the same time: the loop is bound
 // by the VALU, not by latency.
-template <bool REDUCE>
+// MANY (kgs_kzg_open_cosets_many): the n terms are rows of `cols` scalars, the points rows of
+// pcols = 2^k <= cols: term (r, c) takes point (r, c mod pcols), the cached point every polynomial shares.
+template <bool REDUCE, bool MANY = false>
 __global__ void __launch_bounds__(64) k_g1_mul_each(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
-                                                    const uint32_t* __restrict__ sc, uint64_t n) {
+                                                    const uint32_t* __restrict__ sc, uint64_t n, uint64_t cols,
+                                                    uint64_t pcols) {
   KGS_AUX_PRIO();
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  uint64_t pi = i;
+  if (MANY) {
+    const uint64_t r = i / cols;
+    pi = r * pcols + ((i - r * cols) & (pcols - 1));
+  }
   fr k = fr::load(sc + 8 * i);
   if (REDUCE) {
 #pragma unroll 1
@@ -173,7 +216,7 @@ __global__ void __launch_bounds__(64) k_g1_mul_each(uint32_t* __restrict__ out_x
   }
   uint32_t rec[G1NTT_TW_WORDS];
   naf_record(k.v, rec);
-  const g1_aff b = g1_aff::load(in_aff + 16 * i);
+  const g1_aff b = g1_aff::load(in_aff + 16 * pi);
   g1_xyzz r = g1_xyzz::inf();
   if (!b.is_inf()) {
 #pragma unroll 1
@@ -206,15 +249,17 @@ __global__ void __launch_bounds__(64) k_g1_mul_each(uint32_t* __restrict__ out_x
 // in 64 rows. L = 4 (16 KiB, three waves) measured 63.6 ms and was dropped. Half the threads doing twice the
 // work each lose where the launch is latency-bound (6.5 ms against 4.0 ms at 2^13 terms, 5.9 against 6.2 at
 // 2^17): launch_g1_mul_sum takes this kernel from G1_MUL_GROUP_MIN_TERMS terms on.
-template <int L, bool REDUCE>
+// MANY: as k_g1_mul_each's, the point of term (r, i) is in_aff[r pcols + i mod pcols].
+template <int L, bool REDUCE, bool MANY = false>
 __global__ void __launch_bounds__(64) k_g1_mul_group(uint32_t* __restrict__ out_xyzz, const uint32_t* __restrict__ in_aff,
                                                      const uint32_t* __restrict__ sc, uint64_t rows, uint64_t cols,
-                                                     uint64_t ngroups) {
+                                                     uint64_t ngroups, uint64_t pcols) {
   KGS_AUX_PRIO();
   __shared__ uint32_t recs[L][G1NTT_TW_WORDS][64];
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ngroups * cols) return;
   const uint64_t g = t / cols, i = t - g * cols;
+  const uint64_t pc = MANY ? pcols : cols, pi = MANY ? i & (pcols - 1) : i;  // the point rows' width, the column there
   const uint32_t lane = threadIdx.x;
   uint32_t live = 0;  // bit j: row g L + j exists and its point is not the identity
 #pragma unroll 1
@@ -230,7 +275,7 @@ __global__ void __launch_bounds__(64) k_g1_mul_group(uint32_t* __restrict__ out_
     naf_record(k.v, rec);
 #pragma unroll
     for (int w = 0; w < G1NTT_TW_WORDS; w++) recs[j][w][lane] = rec[w];
-    if (!g1_aff::load(in_aff + 16 * (r * cols + i)).is_inf()) live |= 1u << j;
+    if (!g1_aff::load(in_aff + 16 * (r * pc + pi)).is_inf()) live |= 1u << j;
   }
   g1_xyzz acc = g1_xyzz::inf();
   if (live) {
@@ -243,7 +288,7 @@ __global__ void __launch_bounds__(64) k_g1_mul_group(uint32_t* __restrict__ out_
         if (!((live >> j) & 1u)) continue;
         const uint32_t p = (recs[j][w][lane] >> bit) & 1u, m = (recs[j][8 + w][lane] >> bit) & 1u;
         if (p | m) {
-          g1_aff s = g1_aff::load(in_aff + 16 * ((g * L + j) * cols + i));
+          g1_aff s = g1_aff::load(in_aff + 16 * ((g * L + j) * pc + pi));
           if (m) s.y = s.y.neg();
           acc.add_aff(s);
         }
@@ -298,6 +343,52 @@ __global__ void __launch_bounds__(256) k_coset_rows(uint32_t* __restrict__ out, 
   o[1] = hi;
 }
 
+// k_coset_rows for `polys` polynomials (polynomial p: len coefficients at in + 8 stride p), into blocks of
+// 2^logblk >= m elements whose tail is zero: out[((b polys + p) << logblk) + u] = in_p[u l + bitrev_l(b)] for u < m,
+// zero from index len on and for u >= m. Row-major over the polynomials: block b polys + p, so that the
+// transformed rows are the rows x (polys 2^logblk) scalars of the multiply-sum pass. The blocks from l polys up
+// to `nblocks` (the power of two the batched Fr transform wants) are zero. lbits = 0, logblk = logm: the
+// zero-padded coefficients themselves, for the evaluations.
+__global__ void __launch_bounds__(256) k_coset_rows_many(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
+                                                         uint64_t polys, uint64_t stride, uint64_t len, int logm, int lbits,
+                                                         int logblk, uint64_t nblocks) {
+  KGS_AUX_PRIO();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t blk = t >> logblk, u = t & ((1ull << logblk) - 1);
+  if (blk >= nblocks) return;
+  const uint64_t b = blk / polys, p = blk - b * polys;
+  uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+  if ((b >> lbits) == 0 && (u >> logm) == 0) {
+    const uint64_t src = (u << lbits) | (lbits ? __brev((uint32_t)b) >> (32 - lbits) : 0u);
+    if (src < len) {
+      const uint4* q = reinterpret_cast<const uint4*>(in + 8 * (p * stride + src));
+      lo = q[0];
+      hi = q[1];
+    }
+  }
+  uint4* o = reinterpret_cast<uint4*>(out + 8 * t);
+  o[0] = lo;
+  o[1] = hi;
+}
+
+// h[p m + k] = u[p 2m + m - 1 + k] for k < m - 1 and the identity for k = m - 1 (64 B points), p < polys, m = 2^logm
+__global__ void __launch_bounds__(256) k_coset_slice_many(uint32_t* __restrict__ h, const uint32_t* __restrict__ u, int logm,
+                                                          uint64_t total) {
+  KGS_AUX_PRIO();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const uint64_t m = 1ull << logm, p = t >> logm, k = t & (m - 1);
+  uint4 v[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+  if (k < m - 1) {
+    const uint4* q = reinterpret_cast<const uint4*>(u + 16 * (2 * m * p + m - 1 + k));
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = q[j];
+  }
+  uint4* o = reinterpret_cast<uint4*>(h + 16 * t);
+#pragma unroll
+  for (int j = 0; j < 4; j++) o[j] = v[j];
+}
+
 // out[b 2^logm + j] = in[b 2^logm + bitrev(j)] (8 words each), logm >= 1
 __global__ void __launch_bounds__(256) k_bitrev_blocks(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, int logm,
                                                        uint64_t total) {
@@ -347,20 +438,26 @@ void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, u
                        reversed ? (npts >> block_log) - 1 : (uint64_t)0, block_log);
 }
 
+// pcols: 0, every term has a point of its own; else the points are rows of pcols = 2^k columns that the cols / pcols
+// polynomials of a row share (k_g1_mul_each / k_g1_mul_group, MANY; no reduction there)
 template <int L>
 static void launch_g1_mul_group(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars,
-                                uint64_t rows, uint64_t cols, uint64_t ngroups, bool reduce) {
-  auto* kern = reduce ? k_g1_mul_group<L, true> : k_g1_mul_group<L, false>;
-  hipLaunchKernelGGL(kern, dim3(nb(ngroups * cols, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, rows, cols, ngroups);
+                                uint64_t rows, uint64_t cols, uint64_t ngroups, bool reduce, uint64_t pcols) {
+  auto* kern = pcols ? k_g1_mul_group<L, false, true> : reduce ? k_g1_mul_group<L, true> : k_g1_mul_group<L, false>;
+  hipLaunchKernelGGL(kern, dim3(nb(ngroups * cols, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, rows, cols, ngroups,
+                     pcols);
 }
 
-void launch_g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t rows,
-                       uint64_t cols, bool reduce, int group) {
+static void g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t rows,
+                       uint64_t cols, uint64_t pcols, bool reduce, int group) {
   if (!rows || !cols) return;
   if (group == 2 && rows > 1 && rows * cols >= G1_MUL_GROUP_MIN_TERMS) {  // two rows per lane, then their sums
     const uint64_t ngroups = (rows + 1) / 2;
-    launch_g1_mul_group<2>(st, out_xyzz, in_aff, scalars, rows, cols, ngroups, reduce);
+    launch_g1_mul_group<2>(st, out_xyzz, in_aff, scalars, rows, cols, ngroups, reduce, pcols);
     rows = ngroups;
+  } else if (pcols) {
+    hipLaunchKernelGGL((k_g1_mul_each<false, true>), dim3(nb(rows * cols, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars,
+                       rows * cols, cols, pcols);
   } else {
     launch_g1_mul_each(st, out_xyzz, in_aff, scalars, rows * cols, reduce);
   }
@@ -368,6 +465,26 @@ void launch_g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_af
     const uint64_t live = (rows + stride - 1) / stride, ngroups = (live + G1_SUM_FAN - 1) / G1_SUM_FAN;
     hipLaunchKernelGGL(k_g1_col_sum, dim3(nb(ngroups * cols, 64)), dim3(64), 0, st, out_xyzz, rows, cols, stride, ngroups);
   }
+}
+
+void launch_g1_mul_sum(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars, uint64_t rows,
+                       uint64_t cols, bool reduce, int group) {
+  g1_mul_sum(st, out_xyzz, in_aff, scalars, rows, cols, 0, reduce, group);
+}
+
+void launch_g1_mul_sum_many(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars,
+                            uint64_t rows, uint64_t polys, uint64_t pcols, int group) {
+  g1_mul_sum(st, out_xyzz, in_aff, scalars, rows, polys * pcols, pcols, false, group);
+}
+
+void launch_coset_rows_many(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t polys, uint64_t stride, uint64_t len,
+                            int logm, int lbits, int logblk, uint64_t nblocks) {
+  hipLaunchKernelGGL(k_coset_rows_many, dim3(nb(nblocks << logblk)), dim3(256), 0, st, out, in, polys, stride, len, logm,
+                     lbits, logblk, nblocks);
+}
+
+void launch_coset_slice_many(hipStream_t st, uint32_t* h, const uint32_t* u, int logm, uint64_t polys) {
+  hipLaunchKernelGGL(k_coset_slice_many, dim3(nb(polys << logm)), dim3(256), 0, st, h, u, logm, polys << logm);
 }
 
 void launch_coset_rows(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t len, int logm, int lbits) {
@@ -392,7 +509,7 @@ void launch_g1_mul_each(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_a
                         bool reduce) {
   if (!n) return;
   auto* kern = reduce ? k_g1_mul_each<true> : k_g1_mul_each<false>;
-  hipLaunchKernelGGL(kern, dim3(nb(n, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, n);
+  hipLaunchKernelGGL(kern, dim3(nb(n, 64)), dim3(64), 0, st, out_xyzz, in_aff, scalars, n, (uint64_t)0, (uint64_t)0);
 }
 
 void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, int logn,
@@ -428,6 +545,33 @@ void g1_ntt_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uin
     launch_batch_affine(st, out_aff, w.xyzz, w.scratch, n);
   } else if (logn == 0 && out_aff != in_aff) {
     hipMemcpyAsync(out_aff, in_aff, 64, hipMemcpyDeviceToDevice, st);
+  }
+}
+
+void g1_ntt_many_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t polys,
+                     int logn, const uint32_t root_mont[8], int mapping) {
+  const uint64_t n = 1ull << logn, total = polys << logn;
+  if (!polys) return;
+  if (logn == 0) {
+    if (out_aff != in_aff) hipMemcpyAsync(out_aff, in_aff, 64 * total, hipMemcpyDeviceToDevice, st);
+    return;
+  }
+  G1NttWords root, scale{};
+  for (int j = 0; j < 8; j++) root.w[j] = root_mont[j];
+  hipLaunchKernelGGL(k_g1ntt_twiddles, dim3(nb(n / 2 + 1)), dim3(256), 0, st, w.tw, n / 2, root, scale);
+  const uint32_t* src = in_aff;
+  for (int logh = 0; logh < logn; logh++) {
+    const bool uni = mapping != G1NTT_MAP_LANE && g1ntt_many_uniform(polys, logn, logh);
+    const dim3 grid((unsigned)g1ntt_many_blocks(polys, logn, logh, uni));
+    if (uni)
+      hipLaunchKernelGGL(k_g1ntt_stage_many<true>, grid, dim3(G1NTT_MANY_BLOCK), 0, st, w.xyzz, src, w.tw, polys, logh, logn,
+                         logh == 0);
+    else
+      hipLaunchKernelGGL(k_g1ntt_stage_many<false>, grid, dim3(G1NTT_MANY_BLOCK), 0, st, w.xyzz, src, w.tw, polys, logh, logn,
+                         logh == 0);
+    uint32_t* dst = logh == logn - 1 ? out_aff : w.aff;
+    launch_batch_affine(st, dst, w.xyzz, w.scratch, total);
+    src = dst;
   }
 }
 

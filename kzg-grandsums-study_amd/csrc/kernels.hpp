@@ -269,6 +269,25 @@ void launch_bitrev_blocks(hipStream_t st, uint32_t* out, const uint32_t* in, int
 // in reverse order, each block in its own order (npts a multiple of the block)
 void launch_g1_from29(hipStream_t st, uint32_t* out_aff, const uint32_t* in29, uint64_t npts, bool reversed = false,
                       int block_log = 0);
+// The stages of kgs_kzg_open_cosets_many, each one launch for all the polynomials.
+// `polys` transforms of size 2^logn side by side, transform p over the points [p n, (p + 1) n) of in_aff and
+// out_aff (which may alias): g1_ntt_run without a scaling, one twiddle table of size n, the thread mapping of
+// g1ntt_map.hpp (mapping: G1NTT_MAP_AUTO, or G1NTT_MAP_LANE for the A/B). w sized for polys * n points, w.tw
+// for one transform of size n.
+void g1_ntt_many_run(hipStream_t st, const G1NttWork& w, uint32_t* out_aff, const uint32_t* in_aff, uint64_t polys,
+                     int logn, const uint32_t root_mont[8], int mapping);
+// launch_g1_mul_sum over rows x (polys pcols) scalars below r (an Fr kernel's output words) against rows x pcols points,
+// pcols a power of two: out_xyzz[p pcols + i] = sum_r k[r][p pcols + i] * in_aff[r pcols + i]. out_xyzz as
+// launch_g1_mul_sum's for rows x (polys pcols) terms.
+void launch_g1_mul_sum_many(hipStream_t st, uint32_t* out_xyzz, const uint32_t* in_aff, const uint32_t* scalars,
+                            uint64_t rows, uint64_t polys, uint64_t pcols, int group = G1_MUL_SUM_GROUP);
+// launch_coset_rows for polys polynomials (len coefficients each, `stride` elements apart) into nblocks >= l polys
+// blocks of 2^logblk >= m elements, block b polys + p = the row of residue bitrev_l(b) of polynomial p, zero behind
+// its m elements; the blocks from l polys on are zero. lbits = 0, logblk = logm: the zero-padded coefficients.
+void launch_coset_rows_many(hipStream_t st, uint32_t* out, const uint32_t* in, uint64_t polys, uint64_t stride, uint64_t len,
+                            int logm, int lbits, int logblk, uint64_t nblocks);
+// h[p m + k] = u[p 2m + m - 1 + k], k < m - 1, and h[p m + m - 1] = the identity: m = 2^logm points of 64 B
+void launch_coset_slice_many(hipStream_t st, uint32_t* h, const uint32_t* u, int logm, uint64_t polys);
 
 
 // coset_fold.hip (the batch verifier for coset openings)

@@ -347,6 +347,8 @@ struct Job {
   // (copied), the length in rc_len; the coefficients come back in `scal`, the evaluations in `ev`, the verdict in rc_ok
   uint64_t rc_len = 0;
   int rc_ok = 0;
+  // op 14 (kzgOpenCosetsMany): many_polys polynomials of scal.size() / 32 / many_polys coefficients each, packed
+  uint64_t many_polys = 0;
   // proveMulti: the arguments' kinds and borrowed input views
   struct MultiArg {
     int kind = 0;
@@ -537,6 +539,12 @@ static void job_execute(napi_env, void* data) {
     j->ev.resize((size_t)32 << j->ntt_logm);
     j->rc = kgs_kzg_open_cosets(j->ctx, j->scal.data(), j->scal.size() / 32, j->ntt_logm, j->ntt_inverse, j->bases.data(),
                                 j->ev.data());
+  } else if (j->op == 14) {
+    const uint64_t len = j->many_polys ? j->scal.size() / 32 / j->many_polys : 0;
+    j->bases.resize(((size_t)64 << (j->ntt_logm - j->ntt_inverse)) * j->many_polys);
+    j->ev.resize(((size_t)32 << j->ntt_logm) * j->many_polys);
+    j->rc = kgs_kzg_open_cosets_many(j->ctx, j->scal.data(), j->many_polys, len, len, j->ntt_logm, j->ntt_inverse,
+                                     j->bases.data(), j->ev.data());
   } else if (j->op == 12) {
     j->vb_valid.assign(j->cb_index.size() + 1, 0);
     const int rc = kgs_kzg_verify_cosets_batch(j->ctx, j->nbits, j->ntt_inverse, j->com.data(), j->com.size() / 64,
@@ -584,7 +592,7 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->msm_out, 64));
   } else if (j->op == 8) {
     napi_resolve_deferred(env, j->deferred, make_u8(env, j->bases.data(), j->bases.size()));
-  } else if (j->op == 10 || j->op == 11) {
+  } else if (j->op == 10 || j->op == 11 || j->op == 14) {
     napi_value o;
     napi_create_object(env, &o);
     napi_set_named_property(env, o, "proofs", make_u8(env, j->bases.data(), j->bases.size()));
@@ -1224,6 +1232,37 @@ static napi_value KzgOpenCosets(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_kzg_open_cosets");
 }
 
+// kzgOpenCosetsMany(ctx, coefMont, polys, nBits, lBits) -> Promise<{proofs, evals}> over the SRS resident on ctx
+// (kgs_kzg_open_cosets_many): kzgOpenCosets for `polys` polynomials of equal length packed one after the other, in
+// one call; proofs polys x 2^(nBits - lBits) x 64 B, evals polys x 2^nBits x 32 B, polynomial after polynomial
+static napi_value KzgOpenCosetsMany(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  int32_t nbits = -1, lbits = -1;
+  int64_t polys = -1;
+  Job* j = new Job();
+  j->op = 14;
+  j->ctx = get_ctx(env, argv[0]);
+  j->scal = bytes_of(env, argv[1]);
+  napi_get_value_int64(env, argv[2], &polys);
+  napi_get_value_int32(env, argv[3], &nbits);
+  napi_get_value_int32(env, argv[4], &lbits);
+  const bool sizes = nbits >= 0 && nbits <= 23 && lbits >= 0 && lbits <= nbits && polys >= 0 &&
+                     (uint64_t)polys <= ((uint64_t)1 << (24 - nbits));
+  if (!sizes || j->scal.size() % 32 || (polys == 0 ? j->scal.size() != 0 : j->scal.size() / 32 % (size_t)polys != 0) ||
+      (polys && j->scal.size() / 32 / (size_t)polys > ((size_t)1 << nbits))) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgOpenCosetsMany: expected polys x at most 2^nBits Montgomery coefficients of 32 B, "
+                                   "nBits <= 23, lBits <= nBits, polys * 2^nBits <= 2^24");
+    return nullptr;
+  }
+  j->many_polys = (uint64_t)polys;
+  j->ntt_logm = nbits;
+  j->ntt_inverse = lbits;
+  return queue(env, j, "kgs_kzg_open_cosets_many");
+}
+
 // kzgVerifyCoset(commit, nBits, lBits, index, ysMont, proof, srsG1, tauLG2) -> bool (kgs_kzg_verify_coset, host
 // only): the check of one coset opening; srsG1 = the first 2^lBits points [tau^k]_1, tauLG2 = [tau^l]_2
 static napi_value KzgVerifyCoset(napi_env env, napi_callback_info info) {
@@ -1384,6 +1423,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"commitEvals", nullptr, CommitEvals, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgOpenAll", nullptr, KzgOpenAll, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgOpenCosets", nullptr, KzgOpenCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgOpenCosetsMany", nullptr, KzgOpenCosetsMany, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCoset", nullptr, KzgVerifyCoset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCosetsBatch", nullptr, KzgVerifyCosetsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgRecoverCosets", nullptr, KzgRecoverCosets, nullptr, nullptr, nullptr, napi_default, nullptr},

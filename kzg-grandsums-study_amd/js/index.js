@@ -25,6 +25,9 @@ module.exports = {
     // tauLG2) -> bool checks one of them on the host (kgs_kzg_verify_coset)
     kzg_open_cosets: require("./src/backend").kzgOpenCosets,
     kzg_verify_coset: require("./src/backend").kzgVerifyCoset,
+    // kzg_open_cosets_many(pTauFilename, [coefs ..], lBits) -> {proofs: [..], evals: [..]}: kzg_open_cosets for many
+    // polynomials over one domain and SRS in one call, every stage launched once (kgs_kzg_open_cosets_many)
+    kzg_open_cosets_many: require("./src/backend").kzgOpenCosetsMany,
     // kzg_verify_cosets_batch(commits, nBits, lBits, openings, srsG1, tauLG2[, {host, seed}]) -> Promise<{valid, ..}>:
     // many coset openings {commit, index, ys, proof} against one SRS with one pairing check, folded on the GPU
     // (kgs_kzg_verify_cosets_batch)

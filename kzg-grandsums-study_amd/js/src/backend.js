@@ -250,6 +250,40 @@ async function kzgOpenCosets(pTauFilename, coefs, lBits) {
     });
 }
 
+// kzgOpenCosets for many polynomials in one call (kgs_kzg_open_cosets_many: every stage runs once for the whole
+// set, so small polynomials share the latency one call pays alone). coefsList: an array of Uint8Arrays / BigBuffers
+// of Montgomery coefficients; the domain is the smallest 2^k that holds the longest (and at least 2^lBits points),
+// shorter ones are zero-padded, which changes no proof; coefsList.length * 2^k <= 2^24
+// -> Promise<{proofs: [2^(k - lBits) x 64 B ..], evals: [2^k x 32 B ..]}>, entry b what kzgOpenCosets gives for
+// polynomial b on that domain
+async function kzgOpenCosetsMany(pTauFilename, coefsList, lBits) {
+    const key = path.resolve(pTauFilename);
+    if (!Array.isArray(coefsList) || !Number.isInteger(lBits) || lBits < 0 || lBits > 23) {
+        throw new Error("kzg_open_cosets_many: expected an array of coefficient buffers and lBits in 0 .. 23");
+    }
+    if (coefsList.length === 0) return { proofs: [], evals: [] };
+    const cs = coefsList.map(c => contiguous(c));
+    const n =cs.reduce((a, c) => Math.max(a, c.byteLength / 32), 0);
+    if (cs.some(c => c.byteLength % 32 !== 0) || n > (1 << 23)) {
+        throw new Error("kzg_open_cosets_many: the coefficients must be at most 2^23 32-byte elements");
+    }
+    const nBits = Math.max(n > 1 ? Math.ceil(Math.log2(n)) : 0, lBits);
+    if (cs.length * 2 ** nBits > 2 ** 24) {
+        throw new Error("kzg_open_cosets_many: polys * 2^nBits must be at most 2^24");
+    }
+    const packed = new Uint8Array(32 * n * cs.length);
+    cs.forEach((c, b) => packed.set(c, 32 * n * b));
+    return withContext(async slot => {
+        await ensureSrs(slot, key, nBits);
+        const r = await load().kzgOpenCosetsMany(slot.ctx, packed, cs.length, nBits, lBits);
+        const ps = 64 * 2 ** (nBits - lBits), es = 32 * 2 ** nBits;
+        return {
+            proofs: cs.map((_, b) => r.proofs.subarray(ps * b, ps * (b + 1))),
+            evals: cs.map((_, b) => r.evals.subarray(es * b, es * (b + 1))),
+        };
+    });
+}
+
 // The check of one coset opening on the host (kgs_kzg_verify_coset) -> bool. commit / proof: 64 B affine LEM;
 // ysMont: the coset's 2^lBits values, 32 B Montgomery each; srsG1: the first 2^lBits points [tau^k]_1, 64 B
 // affine LEM each; tauLG2: [tau^(2^lBits)]_2, 128 B LEM
@@ -347,4 +381,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgVerifyCoset, kzgVerifyCosetsBatch, kzgRecoverCosets, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgOpenCosetsMany, kzgVerifyCoset, kzgVerifyCosetsBatch, kzgRecoverCosets, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
