@@ -98,31 +98,23 @@ struct DBuf {
 // were loaded for) and the NTT / coset twiddle tables (the largest domain built so far serves every
 // smaller one: stage tables tw[h + t] = w_2h^t do not depend on the maximum domain). Published only
 // after their build has completed (stream synchronised), released when the last context drops them.
-// The Lagrange-basis SRS [L_i(tau)]_1, i < n, of a resident SRS (g1_ntt.cpp, kgs_srs_lagrange): one row in
-// the form msm_points_run reads
-struct LagrangeRow {
+// One row of device points derived from a resident SRS for a domain of n = 2^nbits points and cached on its
+// SrsTables entry (srs_row_cached below): the Lagrange bases, or the SRS side of the openings' Toeplitz product
+struct SrsRow {
   int device = 0;
-  uint32_t* row29 = nullptr;
+  uint32_t* p = nullptr;
   uint64_t n = 0;
-  ~LagrangeRow() {
-    if (row29) {
-      hipSetDevice(device);
-      hipFree(row29);
-    }
+  static std::shared_ptr<SrsRow> make(int device, uint64_t n, size_t bytes) {
+    auto row = std::make_shared<SrsRow>();
+    row->device = device;
+    row->n = n;
+    HC(dev_malloc((void**)&row->p, bytes));
+    return row;
   }
-};
-
-// The SRS side of kgs_kzg_open_all's Toeplitz product for n = 2^nbits (g1_ntt.cpp): the
-// forward G1 transform of size 2n of (s_{n-2}, .., s_0, identity ..) over table row 0, scaled by 1 / 2n;
-// 2n affine points in the 2^256 form, still carrying the row's rho
-struct FkRow {
-  int device = 0;
-  uint32_t* xhat = nullptr;
-  uint64_t n = 0;
-  ~FkRow() {
-    if (xhat) {
+  ~SrsRow() {
+    if (p) {
       hipSetDevice(device);
-      hipFree(xhat);
+      hipFree(p);
     }
   }
 };
@@ -135,14 +127,15 @@ struct SrsTables {
   // slice_world * j only (slice_world == 1: the whole prefix)
   int slice_rank = 0, slice_world = 1;
   MsmTables tb;
-  // nbits -> the Lagrange bases of the first 2^nbits points; read and published under g_reg_mu, built
-  // outside it and published complete, released with the tables
-  std::map<int, std::shared_ptr<LagrangeRow>> lagrange;
-  std::map<int, std::shared_ptr<FkRow>> fk;  // nbits -> kgs_kzg_open_all's row, under the same rules
-  // (nbits, lbits >= 1) -> kgs_kzg_open_cosets' rows (g1_ntt.cpp), under the same rules: the
-  // l = 2^lbits transforms of size 2m = 2n / l of the stride-l subsequences of the SRS side, scaled by 1 / 2m,
-  // 2n points in all; block b of 2m points belongs to the residue bitrev_l(b)
-  std::map<std::pair<int, int>, std::shared_ptr<FkRow>> fk_cosets;
+  // nbits -> the Lagrange-basis SRS [L_i(tau)]_1, i < n (g1_ntt.cpp, kgs_srs_lagrange): n points in the form
+  // msm_points_run reads
+  std::map<int, std::shared_ptr<SrsRow>> lagrange;
+  // (nbits, lbits) -> the SRS side of the openings (kzg_open.cpp); lbits == 0 is
+  // kgs_kzg_open_all's row: the forward G1 transform of size 2n of (s_{n-2}, .., s_0, identity ..) over table
+  // row 0, scaled by 1 / 2n. lbits >= 1 are kgs_kzg_open_cosets' rows: the l = 2^lbits transforms of size
+  // 2m = 2n / l of the stride-l subsequences of that vector, scaled by 1 / 2m; block b of 2m points belongs to
+  // the residue bitrev_l(b). 2n affine points in the 2^256 form either way, still carrying the row's rho
+  std::map<std::pair<int, int>, std::shared_ptr<SrsRow>> fk;
   ~SrsTables() {
     if (tb.table) {
       hipSetDevice(device);
@@ -680,6 +673,16 @@ void prove_rounds(kgs_ctx& c, int nbits, const std::vector<ArgIn>& args, const R
                   uint8_t* ev_out);
 // the SRS preconditions every prover shares word for word
 void check_srs(const kgs_ctx& c, int nbits);
+// The refusals of every call that runs on one plain context only (after its mutex is held). The batch verifier and
+// kgs_g1_lincomb (verify_batch.cpp) accept a sharded context and refuse the rank group alone.
+inline void check_no_group(const kgs_ctx& c, const std::string& fn) {
+  if (c.group) throw KgsError(KGS_E_ARG, fn + " does not run on a context attached to a rank group.");
+}
+inline void check_plain_ctx(const kgs_ctx& c, const char* fn) {
+  check_no_group(c, fn);
+  if (c.shard_world > 1)
+    throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context with MSM sharding (kgs_ctx_set_shard).");
+}
 std::string arg_prefix(int j);  // "argument j: "
 
 // the per-round wall clock (kgs_last_timing) and roctx range of a proof
@@ -721,6 +724,72 @@ struct DrainOnError {
     (void)hipGetLastError();
   }
 };
+
+// The one rule of the rows cached on an SRS (SrsTables::lagrange, ::fk): a row is looked up and published under
+// g_reg_mu (taken after the context's mutex, never the other way round), built outside it on the context's main
+// stream, and published only complete, after the stream has drained. Of two contexts that build the same row at
+// once the first publisher wins and the other's row is released. `build` enqueues the row and returns it; a
+// failed build drains the context (DrainOnError). The caller holds the context and has checked it. Ends with the
+// main stream drained when it built.
+template <class Map, class Build>
+std::shared_ptr<SrsRow> srs_row_cached(kgs_ctx& c, Map& rows, const typename Map::key_type& key, Build build) {
+  {
+    std::lock_guard<std::mutex> lk(g_reg_mu);
+    auto it = rows.find(key);
+    if (it != rows.end()) return it->second;
+  }
+  DrainOnError drain(&c);
+  const std::shared_ptr<SrsRow> row = build();
+  HC(hipStreamSynchronize(c.st));
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  auto& slot = rows[key];
+  if (!slot) slot = row;
+  return slot;
+}
+
+// The two events of a timing helper (kgs_bench_*), destroyed however the helper leaves
+struct EventTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  EventTimer() {
+    HC(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) {
+      hipEventDestroy(e0);
+      throw KgsError(KGS_E_HIP, "HIP error: hipEventCreate failed");
+    }
+  }
+  EventTimer(const EventTimer&) = delete;
+  EventTimer& operator=(const EventTimer&) = delete;
+  ~EventTimer() {
+    hipEventDestroy(e0);
+    hipEventDestroy(e1);
+  }
+  // the milliseconds `body` takes on st, which the call drains
+  template <class Body>
+  double ms(hipStream_t st, Body body) {
+    HC(hipEventRecord(e0, st));
+    body();
+    HC(hipEventRecord(e1, st));
+    check_launch();
+    HC(hipEventSynchronize(e1));
+    float f = 0;
+    HC(hipEventElapsedTime(&f, e0, e1));
+    return f;
+  }
+};
+
+// ------------------------------------------------------------------ G1 transform host side (g1_ntt.cpp)
+constexpr int G1_NTT_LOG_MAX = 24;
+void fr_words(const Fr& x, uint32_t w[8]);
+Fr ntt_root(int logm, bool inverse);  // omega_{2^logm}, or its inverse
+Fr ninv_std(int logm);                // 1 / 2^logm as the standard-form words the kernels take
+// the transform's work buffers ("gn_*" in the context's pool) for 2^logm points
+G1NttWork ntt_work(kgs_ctx& c, int logm);
+// the transform on the main stream (not synchronised); scale: nullptr, or the standard-form factor
+void ntt_enqueue(kgs_ctx& c, uint32_t* out, const uint32_t* in, int logm, bool inverse, const Fr* scale_words);
+// the context holds a whole SRS (not a rank's slice), or the refusals of kgs.h
+void check_whole_srs(const kgs_ctx& c, const char* fn);
+// check_plain_ctx, check_whole_srs, and that SRS can serve 2^nbits Lagrange bases
+void check_lagrange(const kgs_ctx& c, int nbits, const char* fn);
 
 // the single-argument prover (prover.cpp): its checks, the rank-group dispatch, then prove_rounds
 void prove_impl(kgs_ctx& c, const ProveIn& in, uint8_t* com_out, uint8_t* ev_out);

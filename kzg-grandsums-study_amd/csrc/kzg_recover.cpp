@@ -98,12 +98,6 @@ void rc_check_args(kgs_ctx_t* ctx, const char* fn, int nbits, int lbits, const v
                                   std::to_string(need) + " .. m = " + std::to_string(m));
 }
 
-void rc_check_ctx(const kgs_ctx& c, const char* fn) {
-  if (c.group) throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context attached to a rank group.");
-  if (c.shard_world > 1)
-    throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context with MSM sharding (kgs_ctx_set_shard).");
-}
-
 // the flag words after the drain: the refusals they stand for, else the verdict
 int rc_verdict(kgs_ctx& c, const char* fn, const uint32_t* hf, const uint64_t* index, bool device, int nbits, int lbits) {
   const uint64_t m = 1ull << (nbits - lbits);
@@ -140,7 +134,7 @@ int recover_entry(kgs_ctx_t* ctx, int nbits, int lbits, const void* index, const
   const char* fn = device ? "kgs_kzg_recover_cosets_device" : "kgs_kzg_recover_cosets";
   rc_check_args(ctx, fn, nbits, lbits, index, ys, count, len, coef);
   std::lock_guard<std::mutex> lk(ctx->mu);
-  rc_check_ctx(*ctx, fn);
+  check_plain_ctx(*ctx, fn);
   HC(hipSetDevice(ctx->device));
   kgs_ctx& c = *ctx;
   DrainOnError drain(&c);
@@ -198,7 +192,7 @@ int kgs_bench_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const voi
     throw KgsError(KGS_E_ARG, std::string(fn) + ": leaf_log must be 0 or in " + std::to_string(RC_LEAF_LOG_MIN) + " .. " +
                                   std::to_string(RC_LEAF_LOG_MAX));
   std::lock_guard<std::mutex> lk(ctx->mu);
-  rc_check_ctx(*ctx, fn);
+  check_plain_ctx(*ctx, fn);
   HC(hipSetDevice(ctx->device));
   kgs_ctx& c = *ctx;
   DrainOnError drain(&c);
@@ -210,29 +204,19 @@ int kgs_bench_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const voi
   rc_run(c, b, nbits, lbits, (const uint64_t*)d_index, (const uint32_t*)d_ys_mont, count, len, (uint32_t*)d_coef_mont, nullptr,
          leaf_log);
   HC(hipStreamSynchronize(c.st));
-  hipEvent_t e0, e1;
-  HC(hipEventCreate(&e0));
-  HC(hipEventCreate(&e1));
-  for (int r = 0; r < reps; r++) {
-    HC(hipEventRecord(e0, c.st));
-    if (what == 0)
-      rc_run(c, b, nbits, lbits, (const uint64_t*)d_index, (const uint32_t*)d_ys_mont, count, len, (uint32_t*)d_coef_mont,
-             nullptr, leaf_log);
-    else if (what == 1)
-      rc_tree(c, b, (const uint64_t*)d_index, count, logm, leaf_log);
-    else if (what == 2)
-      rc_mside(c, b, count, logm, lbits);
-    else
-      rc_nside(c, b, nbits, lbits, false);
-    HC(hipEventRecord(e1, c.st));
-    check_launch();
-    HC(hipEventSynchronize(e1));
-    float f = 0;
-    HC(hipEventElapsedTime(&f, e0, e1));
-    ms[r] = f;
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
+  EventTimer timer;
+  for (int r = 0; r < reps; r++)
+    ms[r] = timer.ms(c.st, [&] {
+      if (what == 0)
+        rc_run(c, b, nbits, lbits, (const uint64_t*)d_index, (const uint32_t*)d_ys_mont, count, len, (uint32_t*)d_coef_mont,
+               nullptr, leaf_log);
+      else if (what == 1)
+        rc_tree(c, b, (const uint64_t*)d_index, count, logm, leaf_log);
+      else if (what == 2)
+        rc_mside(c, b, count, logm, lbits);
+      else
+        rc_nside(c, b, nbits, lbits, false);
+    });
   c.reset_staging();
   API_END
 }

@@ -359,18 +359,9 @@ int kgs_bench_msm(kgs_ctx_t* ctx, const void* d_scalars_mont, uint64_t n, int re
   uint32_t* dT = ctx->buf("msm_T", (size_t)64 * ctx->tb.c * 128);
   if (!msm_run(ctx->st, ctx->tb, ctx->mw, (const uint32_t*)d_scalars_mont, n, dT))  // warm
     throw KgsError(KGS_E_ARG, "unsupported MSM window");
-  hipEvent_t e0, e1;
-  HC(hipEventCreate(&e0));
-  HC(hipEventCreate(&e1));
-  HC(hipEventRecord(e0, ctx->st));
-  for (int r = 0; r < reps; r++) msm_run(ctx->st, ctx->tb, ctx->mw, (const uint32_t*)d_scalars_mont, n, dT);
-  HC(hipEventRecord(e1, ctx->st));
-  HC(hipEventSynchronize(e1));
-  float f = 0;
-  HC(hipEventElapsedTime(&f, e0, e1));
-  *ms = f;
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
+  *ms = EventTimer().ms(ctx->st, [&] {  // one interval around all the repetitions
+    for (int r = 0; r < reps; r++) msm_run(ctx->st, ctx->tb, ctx->mw, (const uint32_t*)d_scalars_mont, n, dT);
+  });
   API_END
 }
 

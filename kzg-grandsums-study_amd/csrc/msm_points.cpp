@@ -96,9 +96,7 @@ int msm_points_entry(kgs_ctx_t* ctx, const void* points, const void* scalars, bo
     return KGS_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (ctx->group) throw KgsError(KGS_E_ARG, "kgs_msm_points does not run on a context attached to a rank group.");
-  if (ctx->shard_world > 1)
-    throw KgsError(KGS_E_ARG, "kgs_msm_points does not run on a context with MSM sharding (kgs_ctx_set_shard).");
+  check_plain_ctx(*ctx, "kgs_msm_points");
   if (!n) {
     memset(out, 0, 64);
     return KGS_OK;

@@ -368,21 +368,12 @@ int kgs_bench_ntt(kgs_ctx_t* ctx, void* d_buf, int logm, int reps, double* ms) {
   if (logm > ctx->logM) ensure_domain(*ctx, logm);
   uint32_t* a = (uint32_t*)d_buf;
   const uint64_t m = 1ull << logm;
-  hipEvent_t e0, e1;
-  HC(hipEventCreate(&e0));
-  HC(hipEventCreate(&e1));
-  HC(hipEventRecord(e0, ctx->st));
-  for (int r = 0; r < reps; r++) {
-    ntt_dif(ctx->st, a, a, m, logm, nullptr, ctx->tw_fwd, ctx->logM);
-    ntt_dit(ctx->st, a, a, 1, logm, ctx->tw_inv, ctx->logM, nullptr, ctx->invm + 8 * logm);
-  }
-  HC(hipEventRecord(e1, ctx->st));
-  HC(hipEventSynchronize(e1));
-  float f = 0;
-  HC(hipEventElapsedTime(&f, e0, e1));
-  *ms = f;
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
+  *ms = EventTimer().ms(ctx->st, [&] {  // one interval around all the repetitions
+    for (int r = 0; r < reps; r++) {
+      ntt_dif(ctx->st, a, a, m, logm, nullptr, ctx->tw_fwd, ctx->logM);
+      ntt_dit(ctx->st, a, a, 1, logm, ctx->tw_inv, ctx->logM, nullptr, ctx->invm + 8 * logm);
+    }
+  });
   API_END
 }
 

@@ -80,7 +80,7 @@ struct CtxUse {  // the context's mutex and device for the rest of the call (no-
   explicit CtxUse(kgs_ctx* c, const char* what) {
     if (!c) return;
     lk = std::unique_lock<std::mutex>(c->mu);
-    if (c->group) throw KgsError(KGS_E_ARG, std::string(what) + " does not run on a context attached to a rank group.");
+    check_no_group(*c, what);  // MSM sharding is not refused here
     HC(hipSetDevice(c->device));
   }
 };

@@ -362,12 +362,6 @@ struct Bisect {
   }
 };
 
-void check_ctx_free(kgs_ctx* ctx, const char* fn) {
-  if (ctx->group) throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context attached to a rank group.");
-  if (ctx->shard_world > 1)
-    throw KgsError(KGS_E_ARG, std::string(fn) + " does not run on a context with MSM sharding (kgs_ctx_set_shard).");
-}
-
 int verify_cosets_impl(kgs_ctx* ctx, const Batch& b, bool device, const uint8_t* tau_l_g2, const uint8_t* seed32,
                        uint8_t* valid_out, kgs_coset_batch_diag_t* diag) {
   const char* fn = device ? "kgs_kzg_verify_cosets_batch_device" : "kgs_kzg_verify_cosets_batch";
@@ -392,7 +386,7 @@ int verify_cosets_impl(kgs_ctx* ctx, const Batch& b, bool device, const uint8_t*
   std::unique_lock<std::mutex> lk;
   if (ctx) {
     lk = std::unique_lock<std::mutex>(ctx->mu);
-    check_ctx_free(ctx, fn);
+    check_plain_ctx(*ctx, fn);
   }
   if (!b.count) return 1;
 
@@ -482,7 +476,7 @@ int interp_fold_impl(kgs_ctx* ctx, int nbits, int lbits, const void* index, cons
     return KGS_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
-  check_ctx_free(ctx, fn);
+  check_plain_ctx(*ctx, fn);
   if (lbits > COSET_FOLD_LBITS_MAX)
     throw KgsError(KGS_E_ARG, std::string(fn) + ": with a context lbits must be in 0 .. " +
                                   std::to_string(COSET_FOLD_LBITS_MAX));
@@ -564,7 +558,7 @@ int kgs_bench_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const void
       (count << lbits) > CB_MAX_VALUES)
     throw KgsError(KGS_E_ARG, std::string(fn) + ": sizes out of range");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  check_ctx_free(ctx, fn);
+  check_plain_ctx(*ctx, fn);
   HC(hipSetDevice(ctx->device));
   kgs_ctx& c = *ctx;
   DrainOnError drain(ctx);
@@ -572,27 +566,14 @@ int kgs_bench_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const void
   uint32_t* d_small = c.buf("cb_small", 256);
   uint32_t* d_out = c.buf("cb_D", 32ull << lbits);
   HC(hipMemsetAsync(d_small, 0, 256, c.st));
-  hipEvent_t e0, e1;
-  HC(hipEventCreate(&e0));
-  HC(hipEventCreate(&e1));
-  try {
-    for (int r = -1; r < reps; r++) {  // run -1 warms up
-      HC(hipEventRecord(e0, c.st));
+  EventTimer timer;
+  for (int r = -1; r < reps; r++) {  // run -1 warms up
+    const double t = timer.ms(c.st, [&] {
       interp_fold_gpu(c, d_out, nullptr, d_small + 8, (const uint32_t*)d_ys_mont, (const uint64_t*)d_index,
                       (const uint32_t*)d_weights_mont, count, nbits, lbits);
-      HC(hipEventRecord(e1, c.st));
-      HC(hipEventSynchronize(e1));
-      float t = 0;
-      HC(hipEventElapsedTime(&t, e0, e1));
-      if (r >= 0) ms[r] = t;
-    }
-  } catch (...) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    throw;
+    });
+    if (r >= 0) ms[r] = t;
   }
-  HC(hipEventDestroy(e0));
-  HC(hipEventDestroy(e1));
   API_END
 }
 
