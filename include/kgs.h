@@ -856,6 +856,41 @@ int kgs_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const uint64_t*
 /* Same with device pointers (on ctx's device) for index, ys, coef and evals. */
 int kgs_kzg_recover_cosets_device(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
                                   uint64_t count, uint64_t len, void* d_coef_mont, void* d_evals_mont);
+/* ---- recovery of many polynomials in one call. `polys` polynomials of `len` coefficients each, over
+ * one domain (notation above). The cells arrive as kgs_kzg_verify_cosets_batch takes them: cell k < count belongs to
+ * polynomial poly_of[k] < polys (commit_of's type and role), names coset index[k] < m, and row k of ys_mont holds its
+ * l values. Cells come in any order and every polynomial has its own set of cosets. The outputs are laid out as
+ * kgs_kzg_open_cosets_many's input: coef_mont + 32 stride b receives the len coefficients of polynomial b (stride >=
+ * len; the gap between len and stride is not written), evals_mont (if not NULL) its n values p_b(w^k) at
+ * 32 n b, and status_out (if not NULL) one byte per polynomial:
+ *   1  recovered
+ *   0  its cells lie on no polynomial of degree < len
+ *   2  it has fewer than ceil(len / l) cells, possibly none: nothing can be said
+ * For status 0 and 2 that polynomial's outputs are unspecified; every other polynomial's are unaffected. For status 0
+ * and 1 the verdict and every byte equal what kgs_kzg_recover_cosets gives for that polynomial's cells alone.
+ * Returns 1 when every status is 1, else 0 (the same with status_out == NULL). polys == 0 does nothing and returns 1
+ * (after the NULL-ctx refusal no other argument is looked at then, the context's state included);
+ * count == 0 gives status 2 everywhere. Every stage is launched once for all the polynomials, over arrays of polys
+ * rounded up to a power of two blocks (at most twice the memory): the product trees are the levels of one array
+ * stopped at degree m, the transforms run block by block in one launch sequence.
+ *   nbits  0 .. 23;  lbits  0 .. nbits;  len  1 .. n;  polys n <= 2^24;  count <= polys m;  stride >= len
+ *   poly_of  count x uint32;  index  count x uint64;  ys_mont  count x l x 32 B Montgomery, canonical;  all only read
+ * KGS_E_ARG (kgs_last_error names the first offender where there is one): ctx == NULL (there is no host path; no GPU
+ * is touched), a NULL coef_mont, a NULL poly_of, index or ys_mont with count > 0, nbits / lbits / len / polys / count
+ * out of range, stride < len, a rank group, MSM sharding; and, found on the device, the lowest cell with poly_of >=
+ * polys or index >= m, the lowest cell that names a (polynomial, coset) pair a second time, the lowest value (cell, j)
+ * that is not below r. Context contract as for kgs_kzg_recover_cosets, with work buffers of the call's own ("rcm_*"):
+ * the single call's "rc_*" buffers are not touched either. */
+int kgs_kzg_recover_cosets_many(kgs_ctx_t* ctx, int nbits, int lbits, uint64_t polys, const uint32_t* poly_of,
+                                const uint64_t* index, const uint8_t* ys_mont, uint64_t count, uint64_t len,
+                                uint64_t stride, uint8_t* coef_mont /* polys x stride x 32 B */,
+                                uint8_t* evals_mont /* NULL or polys x 2^nbits x 32 B */,
+                                uint8_t* status_out /* NULL or polys B */);
+/* Same with device pointers (on ctx's device) for poly_of, index, ys, coef and evals; status_out stays a host
+ * pointer. */
+int kgs_kzg_recover_cosets_many_device(kgs_ctx_t* ctx, int nbits, int lbits, uint64_t polys, const void* d_poly_of,
+                                       const void* d_index, const void* d_ys_mont, uint64_t count, uint64_t len,
+                                       uint64_t stride, void* d_coef_mont, void* d_evals_mont, uint8_t* status_out);
 /* Keccak-256 (js-sha3 keccak256) */
 int kgs_keccak256(const uint8_t* data, uint64_t len, uint8_t out[32]);
 
@@ -916,6 +951,16 @@ int kgs_bench_coset_interp_fold(kgs_ctx_t* ctx, int nbits, int lbits, const void
 int kgs_bench_kzg_recover_cosets(kgs_ctx_t* ctx, int nbits, int lbits, const void* d_index, const void* d_ys_mont,
                                  uint64_t count, uint64_t len, void* d_coef_mont, int what, int leaf_log, int reps,
                                  double* ms);
+/* `reps` runs of a leg of kgs_kzg_recover_cosets_many_device over device-resident inputs (arguments and ranges as that
+ * call's, polys >= 1; d_coef_mont receives the coefficients), after one whole call, each between two events on ctx's
+ * stream: ms[r] = run r. what: 0 the whole call without evaluations, 1 the marks and the trees, 2 the m-sized side,
+ * 3 the three block transforms of size n and the twist between them alone, 4 the yardstick: polys runs of
+ * kgs_kzg_recover_cosets_device's work, one polynomial after the other, enqueued back to back without the per-call
+ * drain. what 4 takes the cells grouped by ascending polynomial, ceil(len / l) .. m of them for each, and uses the
+ * single call's "rc_*" buffers. */
+int kgs_bench_kzg_recover_cosets_many(kgs_ctx_t* ctx, int nbits, int lbits, uint64_t polys, const void* d_poly_of,
+                                      const void* d_index, const void* d_ys_mont, uint64_t count, uint64_t len,
+                                      uint64_t stride, void* d_coef_mont, int what, int reps, double* ms);
 /* Host-only test hook of kgs_prove's staging copy (no GPU): copies len bytes src -> dst the way a
  * host input vector is staged (256 KiB pieces over the copy pool, spans of `span` bytes reported in
  * order once copied). spans_out[i] receives the byte offset of the i-th reported span (up to max);

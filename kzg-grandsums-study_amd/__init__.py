@@ -226,6 +226,18 @@ def lib():
                                                    ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.POINTER(ctypes.c_double)]
+        L.kgs_kzg_recover_cosets_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, c_u8p, c_u8p]
+        L.kgs_kzg_recover_cosets_many_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                         ctypes.c_void_p, ctypes.c_void_p, c_u8p]
+        L.kgs_bench_kzg_recover_cosets_many.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.POINTER(ctypes.c_double)]
         L.kgs_ptau_read_tau_g2_pow.argtypes = [ctypes.c_char_p, ctypes.c_uint64, c_u8p]
         L.kgs_ctx_set_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.kgs_ctx_set_msm_lanes.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -963,6 +975,27 @@ class Context:
         or None, to 2^nbits x 32 writable bytes. Returns the verdict as a bool."""
         return _check(lib().kgs_kzg_recover_cosets_device(self._h, nbits, lbits, d_index, d_ys, count, length, d_coef,
                                                           d_evals)) == 1
+
+    def kzg_recover_cosets_many(self, nbits, lbits, poly_of, index, ys_mont, length, polys, evals=False, stride=None,
+                                coefs_out=None):
+        """Many polynomials back from their cells in one call (kgs_kzg_recover_cosets_many): see the module-level
+        kzg_recover_cosets_many. stride (>= length, default length): polynomial b's coefficients go to element
+        stride * b of the result; coefs_out: a bytearray of polys * stride * 32 B that receives them in place (the gaps
+        between length and stride are not written) and is returned as bytes."""
+        return _kzg_recover_cosets_many(self._h, nbits, lbits, poly_of, index, ys_mont, length, polys, evals, stride,
+                                        coefs_out)
+
+    def kzg_recover_cosets_many_device(self, nbits, lbits, polys, d_poly_of, d_index, d_ys, count, length, stride, d_coef,
+                                       d_evals=None, status=True):
+        """Device-resident twin (kgs_kzg_recover_cosets_many_device): device pointers (ints) to count x uint32
+        polynomial numbers, count x uint64 coset indices and count * 2^lbits x 32 B Montgomery values, all only read,
+        to polys * stride x 32 writable bytes (polynomial b at 32 * stride * b; only its first `length` elements are
+        written) and, or None, to polys * 2^nbits x 32 writable bytes. Returns (all recovered, list of statuses), or
+        with status=False (status_out NULL) the bool alone."""
+        st = ctypes.create_string_buffer(max(polys, 1)) if status else None
+        rc = _check(lib().kgs_kzg_recover_cosets_many_device(self._h, nbits, lbits, polys, d_poly_of, d_index, d_ys, count,
+                                                             length, stride, d_coef, d_evals, st))
+        return (rc == 1, list(st.raw[:polys])) if status else rc == 1
 
     def last_exchange(self):
         """Exchanges of the last proof (kgs_last_exchange): all-to-all count / summed span ms / bytes
@@ -1800,6 +1833,48 @@ def kzg_recover_cosets(nbits, lbits, index, ys_mont, length, evals=False, device
     Montgomery coefficients and p(w^k) in natural order. ok is False when the values lie on no polynomial of
     degree < length; the other results then mean nothing. Needs no SRS."""
     return _kzg_recover_cosets(_context(device).handle, nbits, lbits, index, ys_mont, length, evals)
+
+
+def _kzg_recover_cosets_many(handle, nbits, lbits, poly_of, index, ys_mont, length, polys, evals, stride, coefs_out):
+    poly_of, index = list(poly_of), list(index)
+    count = len(index)
+    if len(poly_of) != count:
+        raise ValueError("poly_of and index hold one entry per cell")
+    ok = 0 <= nbits <= 23 and 0 <= lbits <= nbits  # else the library refuses before it reads or writes
+    if ok and len(ys_mont) != (32 << lbits) * count:
+        raise ValueError("ys_mont holds len(index) * 2^lbits 32-byte elements")
+    stride = length if stride is None else stride
+    fits = ok and 1 <= length <= 1 << nbits and stride >= length and 0 <= polys << nbits <= 1 << 24
+    if coefs_out is None:
+        coef = ctypes.create_string_buffer(max(32 * stride * polys, 32) if fits else 32)
+        pcoef, kcoef = coef, None
+    else:
+        if not fits or len(coefs_out) != 32 * stride * polys:
+            raise ValueError("coefs_out holds polys * stride 32-byte elements")
+        pcoef, kcoef = _ptr(coefs_out)
+    ev = ctypes.create_string_buffer(max((32 << nbits) * polys, 32) if fits else 32) if evals else None
+    status = ctypes.create_string_buffer(max(polys, 1) if fits else 1)
+    po = (ctypes.c_uint32 * max(count, 1))(*poly_of)
+    idx = (ctypes.c_uint64 * max(count, 1))(*index)
+    py, ky = _ptr(ys_mont) if len(ys_mont) else (None, None)  # read in place
+    _check(lib().kgs_kzg_recover_cosets_many(handle, nbits, lbits, polys, ctypes.cast(po, ctypes.c_void_p),
+                                             ctypes.cast(idx, ctypes.c_void_p), py, count, length, stride, pcoef, ev,
+                                             status))
+    del ky, kcoef
+    out = bytes(coefs_out) if coefs_out is not None else coef.raw[:32 * stride * polys]
+    return list(status.raw[:polys]), out, (ev.raw[:(32 << nbits) * polys] if evals else None)
+
+
+def kzg_recover_cosets_many(nbits, lbits, poly_of, index, ys_mont, length, polys, evals=False, device=0):
+    """kzg_recover_cosets for `polys` polynomials of `length` coefficients in one call (kgs_kzg_recover_cosets_many).
+    The cells come as the batch verifier takes them: cell k belongs to polynomial poly_of[k] < polys, names coset
+    index[k] < m = 2^(nbits - lbits), and row k of ys_mont holds its 2^lbits Montgomery values; any order, every
+    polynomial its own set of cosets. Returns (status, coefs, evals): one status per polynomial (1 recovered, 0 its
+    cells lie on no polynomial of degree < length, 2 fewer than ceil(length / 2^lbits) cells), polys x length x 32 B
+    Montgomery coefficients, polynomial after polynomial, and with evals=True polys x 2^nbits x 32 B values in natural
+    order (else None). The bytes of a polynomial with status 0 or 2 mean nothing. Needs no SRS."""
+    return _kzg_recover_cosets_many(_context(device).handle, nbits, lbits, poly_of, index, ys_mont, length, polys, evals,
+                                    None, None)
 
 
 def grandsum_verifier(pTauFilename, proof, nBits):

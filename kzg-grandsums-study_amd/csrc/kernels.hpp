@@ -358,5 +358,28 @@ void launch_rc_batch_inv(hipStream_t st, uint32_t* out, const uint32_t* in, uint
 void launch_rc_divide(hipStream_t st, uint32_t* data, const uint32_t* inv, int lbits, uint64_t n);
 // coef[j] = q[j] for j < len; flags[RC_FLAG_HIGH] = 1 if q[j] != 0 for some len <= j < n
 void launch_rc_check_copy(hipStream_t st, uint32_t* coef, const uint32_t* q, uint64_t len, uint64_t n, uint32_t* flags);
+// kgs_kzg_recover_cosets_many: P = 2^logP >= polys polynomials side by side, the arrays of P m slots
+// (2^logtotal with logtotal = logP + logm) or of P n elements (logtotal = logP + nbits). launch_rc_level,
+// launch_rc_batch_inv and launch_rc_divide serve these arrays as they are.
+// row_of (P m words preset to RC_NONE): the lowest cell naming (poly_of[k], index[k]); cnt (P words preset to 0): the
+// distinct cosets of each polynomial; flags[RC_FLAG_INDEX]: the lowest cell with poly_of >= polys or index >= m;
+// flags[RC_FLAG_DUP]: the lowest cell naming a pair again
+void launch_rcm_mark(hipStream_t st, uint32_t* row_of, uint32_t* flags, uint32_t* cnt, const uint32_t* poly_of,
+                     const uint64_t* index, uint64_t count, uint64_t polys, uint64_t m);
+// launch_rc_leaves over the 2^logtotal slots, a_i from the slot's index mod m; leaf_log <= min(logm, RC_LEAF_LOG_MAX)
+void launch_rcm_leaves(hipStream_t st, uint32_t* T, const uint32_t* row_of, const uint32_t* tw_fwd, int logtotal, int logm,
+                       int leaf_log);
+// launch_rc_zcoef per block of m: block b's root is Y^cnt[b] z_b(Y)
+void launch_rcm_zcoef(hipStream_t st, uint32_t* zc, uint32_t* zs, const uint32_t* T, const uint32_t* cnt, int logtotal,
+                      int logm, const uint32_t* coset_pow, int lbits);
+// out[b n + bitrev_n(i + m j)] = ys[row_of[b m + i] l + j] * zev[b m + bitrev_m(i)], zero on a missing coset; a value
+// >= r as launch_rc_scatter takes it
+void launch_rcm_scatter(hipStream_t st, uint32_t* out, const uint32_t* ys, const uint32_t* row_of, const uint32_t* zev,
+                        uint32_t* flags, int logtotal, int logm, int lbits);
+// data[x] *= tab[x mod n], x < 2^logtotal
+void launch_rcm_twist(hipStream_t st, uint32_t* data, const uint32_t* tab, int logtotal, int nbits);
+// coef[b stride + j] = q[b n + j] ipow[j] for j < len, b < polys; high[b] = 1 if q[b n + j] != 0 for some len <= j < n
+void launch_rcm_check_copy(hipStream_t st, uint32_t* coef, const uint32_t* q, const uint32_t* ipow, uint64_t len,
+                           uint64_t stride, int nbits, uint64_t polys, uint32_t* high);
 
 }  // namespace kgs

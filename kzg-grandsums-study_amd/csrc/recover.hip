@@ -12,6 +12,7 @@
 //   k_rc_scatter   E Z on the domain, natural order: y_{k,j} z(a_i) at i + m j, zero on a missing coset
 //   k_rc_divide    times 1 / z(g^l a_i) in the forward transform's bit-reversed order
 //   k_rc_check_copy   the first len coefficients out; flags a nonzero one from len on
+// and, further down, the k_rcm_* kernels of kgs_kzg_recover_cosets_many.
 //
 // Every product is field.hpp's canonical Montgomery product and every stored value is canonical: the kernels
 // here are bound by their HBM traffic (or, the leaves, by LDS round trips), not by the multiplier.
@@ -250,6 +251,153 @@ __global__ void __launch_bounds__(256)
     flags[RC_FLAG_HIGH] = 1;
 }
 
+// ---------------------------------------------------------------- kgs_kzg_recover_cosets_many
+// P = polys rounded up to a power of two polynomials side by side: row_of, T, zc / zs / inv hold P blocks of m, the
+// size-n array P blocks of n. The levels (launch_rc_level), the batch inversion and the division (inv[x >> lbits] is
+// block b's inverse at (x mod n) >> lbits) are the single call's launches over the longer arrays; the kernels below
+// are the ones that need to know where a polynomial ends.
+//
+//   k_rcm_mark        row_of[b m + i] = the lowest cell naming (b, i); cnt[b] = its distinct cosets; the two flags
+//   k_rcm_leaf        k_rc_leaf with a_i from the slot's index mod m: a leaf (min(B, m) slots) never spans two polynomials
+//   k_rcm_zcoef       k_rc_zcoef per block, each root with its own count
+//   k_rcm_scatter     E_b Z_b into block b of the size-n array at the bit-reversed position within the block
+//   k_rcm_twist       times g^j, j the position within the block
+//   k_rcm_check_copy  times g^-j, the first len coefficients to the strided output, one flag per polynomial
+
+__global__ void __launch_bounds__(256)
+    k_rcm_mark(uint32_t* __restrict__ row_of, uint32_t* __restrict__ flags, uint32_t* __restrict__ cnt,
+               const uint32_t* __restrict__ poly_of, const uint64_t* __restrict__ index, uint64_t count, uint64_t polys,
+               uint64_t m) {
+  KGS_AUX_PRIO();
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= count) return;
+  const uint64_t b = poly_of[k], i = index[k];
+  if (b >= polys || i >= m) {
+    atomicMin(flags + RC_FLAG_INDEX, (uint32_t)k);
+    return;
+  }
+  // as k_rc_mark: the later of two cells that name a pair is the offender, the minimum the one reported. Only the
+  // first cell to arrive at a pair counts it, so cnt[b] <= m whatever the input holds
+  const uint32_t prev = atomicMin(row_of + b * m + i, (uint32_t)k);
+  if (prev != RC_NONE)
+    atomicMin(flags + RC_FLAG_DUP, prev > (uint32_t)k ? prev : (uint32_t)k);
+  else
+    atomicAdd(cnt + b, 1u);
+}
+
+// Block b: slots [b B, (b + 1) B) of the P m slots, B = blockDim.x a power of two that divides m. k_rc_leaf's body
+// with one expression changed, a_i = w_m^(slot mod m): the single call's kernel stays the code DESIGN.md §22 measured,
+// so the two bodies are kept in step by hand. A change to the steps of one belongs in the other too.
+__global__ void __launch_bounds__(RC_LEAF_MAX)
+    k_rcm_leaf(uint32_t* __restrict__ T, const uint32_t* __restrict__ row_of, const uint32_t* __restrict__ tw, int logm) {
+  KGS_AUX_PRIO();
+  extern __shared__ __attribute__((aligned(16))) uint4 rc_sh[];
+  const int B = blockDim.x, t = threadIdx.x;
+  uint4* cbuf = rc_sh;              // 2 buffers x 2 planes x B
+  uint4* abuf = rc_sh + 4 * B;      // 2 planes x B
+  uint32_t* miss = reinterpret_cast<uint32_t*>(rc_sh + 6 * B);
+  const uint64_t slot = (uint64_t)blockIdx.x * B + t, half = (1ull << logm) >> 1;
+  const bool missing = row_of[slot] == RC_NONE;
+  miss[t] = missing;
+  if (missing) {
+    fr a = fr::one();
+    if (logm) {
+      const uint64_t i = slot & ((1ull << logm) - 1);
+      const bool hi = i >= half;
+      a = fr::load(tw + 8 * (half + (hi ? i - half : i)));
+      if (hi) a = a.neg();
+    }
+    rc_lds_put(abuf, B, t, a);
+  }
+  __syncthreads();
+  fr c = fr::zero();
+  int deg = 0, buf = 0;
+  for (int i = 0; i < B; i++) {
+    if (!miss[i]) continue;  // uniform over the block
+    const fr cur = t == deg ? fr::one() : c;
+    uint4* cb = cbuf + 2 * B * buf;
+    rc_lds_put(cb, B, t, cur);
+    __syncthreads();
+    if (t <= deg + 1) {
+      const fr prev = t ? rc_lds_get(cb, B, t - 1) : fr::zero();
+      c = prev - rc_lds_get(abuf, B, i) * cur;
+    }
+    deg++;
+    buf ^= 1;
+  }
+  uint32_t* out = T + 8 * ((uint64_t)blockIdx.x * B);
+  if (t < deg) c.store(out + 8 * (B - deg + t));
+  if (t < B - deg) fr::zero().store(out + 8 * t);
+}
+
+// Block b of T is Y^cnt[b] z_b(Y) without its leading 1. cnt[b] = 0 (a polynomial with no cell, and the padding up to
+// P) leaves no z of degree < m: its m low coefficients are stored as they are, and the status comes from the count.
+__global__ void __launch_bounds__(256)
+    k_rcm_zcoef(uint32_t* __restrict__ zc, uint32_t* __restrict__ zs, const uint32_t* __restrict__ T,
+                const uint32_t* __restrict__ cnt, int logm, uint64_t total, const uint32_t* __restrict__ coset_pow,
+                int lbits) {
+  KGS_AUX_PRIO();
+  const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= total) return;
+  const uint64_t m = 1ull << logm, b = x >> logm, t = x & (m - 1);
+  uint64_t have = cnt[b];
+  if (have > m) have = m;
+  const uint64_t dz = m - have;
+  const fr v = t < dz ? fr::load(T + 8 * ((b << logm) + have + t)) : t == dz ? fr::one() : fr::zero();
+  v.store(zc + 8 * x);
+  (v * fr::load(coset_pow + 8 * (t << lbits))).store(zs + 8 * x);
+}
+
+// Output position o of block b is domain point x = bitrev_n(o): coset i = x mod m = bitrev_m(o >> lbits), value
+// j = x / m = bitrev_l(o mod l). So the l consecutive outputs o share one cell, whose row they read whole (permuted),
+// and z_b(a_i) sits at (o >> lbits) of the size-m transform's own order: the writes are coalesced.
+__global__ void __launch_bounds__(256)
+    k_rcm_scatter(uint32_t* __restrict__ out, const uint32_t* __restrict__ ys, const uint32_t* __restrict__ row_of,
+                  const uint32_t* __restrict__ zev, uint32_t* __restrict__ flags, int logm, int lbits, uint64_t total) {
+  KGS_AUX_PRIO();
+  const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= total) return;
+  const uint64_t u = x >> lbits;  // b m + (o >> lbits)
+  const uint32_t ub = (uint32_t)(u & ((1ull << logm) - 1));
+  const uint32_t i = logm ? __brev(ub) >> (32 - logm) : 0;
+  const uint32_t jb = (uint32_t)(x & ((1ull << lbits) - 1));
+  const uint32_t j = lbits ? __brev(jb) >> (32 - lbits) : 0;
+  const uint32_t k = row_of[u - ub + i];
+  fr v = fr::zero();
+  if (k != RC_NONE) {
+    const uint64_t e = ((uint64_t)k << lbits) + j;
+    const fr y = fr::load(ys + 8 * e);
+    if (!rc_canonical(y))
+      atomicMin(flags + RC_FLAG_VALUE, (uint32_t)e);
+    else
+      v = y * fr::load(zev + 8 * u);
+  }
+  v.store(out + 8 * x);
+}
+
+__global__ void __launch_bounds__(256)
+    k_rcm_twist(uint32_t* __restrict__ data, const uint32_t* __restrict__ tab, int nbits, uint64_t total) {
+  KGS_AUX_PRIO();
+  const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= total) return;
+  (fr::load(data + 8 * x) * fr::load(tab + 8 * (x & ((1ull << nbits) - 1)))).store(data + 8 * x);
+}
+
+// q: polys blocks of n coefficients of q_b(g X). g^-j is not zero, so the check from len on needs no product.
+__global__ void __launch_bounds__(256)
+    k_rcm_check_copy(uint32_t* __restrict__ coef, const uint32_t* __restrict__ q, const uint32_t* __restrict__ ipow,
+                     uint64_t len, uint64_t stride, int nbits, uint64_t total, uint32_t* __restrict__ high) {
+  KGS_AUX_PRIO();
+  const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= total) return;
+  const uint64_t b = x >> nbits, j = x & ((1ull << nbits) - 1);
+  const fr v = fr::load(q + 8 * x);
+  if (j < len)
+    (v * fr::load(ipow + 8 * j)).store(coef + 8 * (b * stride + j));
+  else if (!v.is_zero())
+    high[b] = 1;
+}
+
 void launch_rc_mark(hipStream_t st, uint32_t* row_of, uint32_t* flags, const uint64_t* index, uint64_t count, uint64_t m) {
   hipLaunchKernelGGL(k_rc_mark, dim3(rc_nb(count)), dim3(256), 0, st, row_of, flags, index, count, m);
 }
@@ -290,6 +438,42 @@ void launch_rc_batch_inv(hipStream_t st, uint32_t* out, const uint32_t* in, uint
 
 void launch_rc_check_copy(hipStream_t st, uint32_t* coef, const uint32_t* q, uint64_t len, uint64_t n, uint32_t* flags) {
   hipLaunchKernelGGL(k_rc_check_copy, dim3(rc_nb(n)), dim3(256), 0, st, coef, q, len, n, flags);
+}
+
+void launch_rcm_mark(hipStream_t st, uint32_t* row_of, uint32_t* flags, uint32_t* cnt, const uint32_t* poly_of,
+                     const uint64_t* index, uint64_t count, uint64_t polys, uint64_t m) {
+  if (!count) return;
+  hipLaunchKernelGGL(k_rcm_mark, dim3(rc_nb(count)), dim3(256), 0, st, row_of, flags, cnt, poly_of, index, count, polys, m);
+}
+
+void launch_rcm_leaves(hipStream_t st, uint32_t* T, const uint32_t* row_of, const uint32_t* tw_fwd, int logtotal, int logm,
+                       int leaf_log) {
+  const unsigned B = 1u << leaf_log;
+  hipLaunchKernelGGL(k_rcm_leaf, dim3((unsigned)((1ull << logtotal) >> leaf_log)), dim3(B), rc_leaf_lds_bytes(leaf_log), st, T,
+                     row_of, tw_fwd, logm);
+}
+
+void launch_rcm_zcoef(hipStream_t st, uint32_t* zc, uint32_t* zs, const uint32_t* T, const uint32_t* cnt, int logtotal,
+                      int logm, const uint32_t* coset_pow, int lbits) {
+  const uint64_t total = 1ull << logtotal;
+  hipLaunchKernelGGL(k_rcm_zcoef, dim3(rc_nb(total)), dim3(256), 0, st, zc, zs, T, cnt, logm, total, coset_pow, lbits);
+}
+
+void launch_rcm_scatter(hipStream_t st, uint32_t* out, const uint32_t* ys, const uint32_t* row_of, const uint32_t* zev,
+                        uint32_t* flags, int logtotal, int logm, int lbits) {
+  const uint64_t total = 1ull << logtotal;
+  hipLaunchKernelGGL(k_rcm_scatter, dim3(rc_nb(total)), dim3(256), 0, st, out, ys, row_of, zev, flags, logm, lbits, total);
+}
+
+void launch_rcm_twist(hipStream_t st, uint32_t* data, const uint32_t* tab, int logtotal, int nbits) {
+  const uint64_t total = 1ull << logtotal;
+  hipLaunchKernelGGL(k_rcm_twist, dim3(rc_nb(total)), dim3(256), 0, st, data, tab, nbits, total);
+}
+
+void launch_rcm_check_copy(hipStream_t st, uint32_t* coef, const uint32_t* q, const uint32_t* ipow, uint64_t len,
+                           uint64_t stride, int nbits, uint64_t polys, uint32_t* high) {
+  const uint64_t total = polys << nbits;
+  hipLaunchKernelGGL(k_rcm_check_copy, dim3(rc_nb(total)), dim3(256), 0, st, coef, q, ipow, len, stride, nbits, total, high);
 }
 
 }  // namespace kgs

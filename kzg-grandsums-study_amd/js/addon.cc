@@ -560,6 +560,14 @@ static void job_execute(napi_env, void* data) {
                                           j->cb_index.size(), j->rc_len, j->scal.data(), j->ev.data());
     j->rc_ok = rc == 1;
     j->rc = rc < 0 ? rc : KGS_OK;
+  } else if (j->op == 15) {
+    j->scal.resize(32 * (size_t)j->rc_len * j->many_polys);
+    j->ev.resize(((size_t)32 << j->ntt_logm) * j->many_polys);
+    j->vb_valid.assign(j->many_polys + 1, 0);
+    const int rc = kgs_kzg_recover_cosets_many(j->ctx, j->ntt_logm, j->ntt_inverse, j->many_polys, j->cb_commit_of.data(),
+                                               j->cb_index.data(), j->cb_ys.data(), j->cb_index.size(), j->rc_len,
+                                               j->rc_len, j->scal.data(), j->ev.data(), j->vb_valid.data());
+    j->rc = rc < 0 ? rc : KGS_OK;
   } else {
     if (!prepare_prove(j)) return;
     std::string e;
@@ -603,6 +611,13 @@ static void job_complete(napi_env env, napi_status, void* data) {
     napi_create_object(env, &o);
     napi_get_boolean(env, j->rc_ok != 0, &v);
     napi_set_named_property(env, o, "ok", v);
+    napi_set_named_property(env, o, "coefs", make_u8(env, j->scal.data(), j->scal.size()));
+    napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
+    napi_resolve_deferred(env, j->deferred, o);
+  } else if (j->op == 15) {
+    napi_value o;
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "status", make_u8(env, j->vb_valid.data(), j->many_polys));
     napi_set_named_property(env, o, "coefs", make_u8(env, j->scal.data(), j->scal.size()));
     napi_set_named_property(env, o, "evals", make_u8(env, j->ev.data(), j->ev.size()));
     napi_resolve_deferred(env, j->deferred, o);
@@ -1386,6 +1401,56 @@ static napi_value KzgRecoverCosets(napi_env env, napi_callback_info info) {
   return queue(env, j, "kgs_kzg_recover_cosets");
 }
 
+// kzgRecoverCosetsMany(ctx, nBits, lBits, polyOf, index, ysMont, length, polys) -> Promise<{status, coefs, evals}>
+// (kgs_kzg_recover_cosets_many): cell k belongs to polynomial polyOf[k] < polys and names coset index[k]; ysMont count *
+// 2^lBits x 32 B Montgomery values; status polys bytes (1 recovered, 0 no such polynomial, 2 too few cells), coefs
+// polys x length x 32 B, evals polys x 2^nBits x 32 B
+static napi_value KzgRecoverCosetsMany(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Job* j = new Job();
+  j->op = 15;
+  j->ctx = get_ctx(env, argv[0]);
+  int32_t nbits = -1, lbits = -1;
+  int64_t len = -1, polys = -1;
+  napi_get_value_int32(env, argv[1], &nbits);
+  napi_get_value_int32(env, argv[2], &lbits);
+  uint32_t np = 0, ni = 0;
+  napi_get_array_length(env, argv[3], &np);
+  napi_get_array_length(env, argv[4], &ni);
+  bool ok = nbits >= 0 && nbits <= 23 && lbits >= 0 && lbits <= nbits && np == ni;
+  for (uint32_t k = 0; ok && k < ni; k++) {
+    napi_value v;
+    int64_t b = -1, i = -1;
+    napi_get_element(env, argv[3], k, &v);
+    napi_get_value_int64(env, v, &b);
+    napi_get_element(env, argv[4], k, &v);
+    napi_get_value_int64(env, v, &i);
+    ok = b >= 0 && b <= 0xFFFFFFFFll && i >= 0;
+    j->cb_commit_of.push_back((uint32_t)b);
+    j->cb_index.push_back((uint64_t)i);
+  }
+  j->cb_ys = bytes_of(env, argv[5]);
+  napi_get_value_int64(env, argv[6], &len);
+  napi_get_value_int64(env, argv[7], &polys);
+  if (!ok || len < 1 || len > ((int64_t)1 << nbits) || polys < 0 || polys > ((int64_t)1 << 24 >> nbits) ||
+      j->cb_ys.size() != ((size_t)32 * ni << lbits)) {
+    delete j;
+    napi_throw_error(env, nullptr, "kzgRecoverCosetsMany: expected nBits <= 23, lBits <= nBits, one polynomial number and one coset index per cell, count * 2^lBits x 32 B values, 1 <= length <= 2^nBits, polys * 2^nBits <= 2^24");
+    return nullptr;
+  }
+  j->ntt_logm = nbits;
+  j->ntt_inverse = lbits;
+  j->rc_len = (uint64_t)len;
+  j->many_polys = (uint64_t)polys;
+  // the library takes NULL for an empty buffer; a vector's data() may be anything then
+  j->cb_commit_of.reserve(1);
+  j->cb_index.reserve(1);
+  j->cb_ys.reserve(1);
+  return queue(env, j, "kgs_kzg_recover_cosets_many");
+}
+
 // lastTiming(ctx) -> [round 1..5 ms, -, input copy, prover, write-back wait] of the context's last
 // kgs_prove call (kgs_last_timing; diagnostics, call when the context is idle)
 static napi_value LastTiming(napi_env env, napi_callback_info info) {
@@ -1427,6 +1492,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"kzgVerifyCoset", nullptr, KzgVerifyCoset, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgVerifyCosetsBatch", nullptr, KzgVerifyCosetsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"kzgRecoverCosets", nullptr, KzgRecoverCosets, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"kzgRecoverCosetsMany", nullptr, KzgRecoverCosetsMany, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"proveGroup", nullptr, ProveGroup, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lastTiming", nullptr, LastTiming, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ctxSetMsmLanes", nullptr, CtxSetMsmLanes, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -35,6 +35,10 @@ module.exports = {
     // kzg_recover_cosets(nBits, lBits, cells, length) -> Promise<{ok, coefs, evals}>: the polynomial of `length`
     // coefficients through the cells {index, ys} it is given, rebuilt on the GPU (kgs_kzg_recover_cosets)
     kzg_recover_cosets: require("./src/backend").kzgRecoverCosets,
+    // kzg_recover_cosets_many(nBits, lBits, cells, length, polys) -> Promise<{status, coefs, evals}>: `polys`
+    // polynomials of `length` coefficients each through the cells {poly, index, ys} they are given, rebuilt on the GPU
+    // in one call (kgs_kzg_recover_cosets_many); status holds 1 / 0 / 2 per polynomial
+    kzg_recover_cosets_many: require("./src/backend").kzgRecoverCosetsMany,
     // one proof of several arguments of any kinds over one domain (kgs_prove_multi / kgs_verify_multi)
     mset_eq_kzg_multi_prover: require("./src/multi/mset_eq_kzg_multi_prover"),
     mset_eq_kzg_multi_verifier: require("./src/multi/mset_eq_kzg_multi_verifier"),

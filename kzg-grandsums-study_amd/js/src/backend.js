@@ -329,6 +329,18 @@ async function kzgRecoverCosets(nBits, lBits, cells, length) {
         new Uint8Array(ys), length));
 }
 
+// `polys` polynomials of `length` coefficients each back from their cells in one call (kgs_kzg_recover_cosets_many;
+// needs no SRS) -> Promise<{status: polys bytes (1 recovered, 0 the cells lie on no polynomial of degree < length,
+// 2 fewer than ceil(length / 2^lBits) cells), coefs: polys x length x 32 B Montgomery, evals: polys x 2^nBits x 32 B
+// Montgomery}>. cells: an array of {poly (< polys), index (the coset, each at most once per polynomial), ys (its
+// 2^lBits values)}, in any order: the batch verifier's openings with `commit` as `poly`. The bytes of a polynomial
+// whose status is not 1 mean nothing.
+async function kzgRecoverCosetsMany(nBits, lBits, cells, length, polys) {
+    const ys = Buffer.concat(cells.map(c => Buffer.from(contiguous(c.ys))));
+    return withContext(slot => load().kzgRecoverCosetsMany(slot.ctx, nBits, lBits, cells.map(c => c.poly),
+        cells.map(c => c.index), new Uint8Array(ys), length, polys));
+}
+
 // Large proofs over several GPUs from this one Node process: with KGS_JS_SHARD_RANKS = W >= 2, a
 // proof of at least 2^KGS_JS_SHARD_MIN_NBITS elements (default 22) runs on W contexts (rank r on
 // device r mod #devices) joined by an in-process rank group (kgs_group_create_local +
@@ -381,4 +393,4 @@ function poolInfo() {
              idle: pool.idle.length, waiting: pool.waiters.length };
 }
 
-module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgOpenCosetsMany, kzgVerifyCoset, kzgVerifyCosetsBatch, kzgRecoverCosets, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
+module.exports = { load, ptauPower, prove, proveMulti, commitEvals, kzgOpenAll, kzgOpenCosets, kzgOpenCosetsMany, kzgVerifyCoset, kzgVerifyCosetsBatch, kzgRecoverCosets, kzgRecoverCosetsMany, withContext, poolInfo, diag, GRANDSUM: 0, GRANDPRODUCT: 1, LOOKUP: 2 };
