@@ -432,6 +432,21 @@ int kgs_ntt(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logm,
 #define KGS_NTT_INPLACE 16
 #define KGS_NTT_INFLIGHT 32
 int kgs_ntt_ex(kgs_ctx_t* ctx, const uint8_t* in_mont, uint64_t in_len, uint8_t* out_mont, int logm, int flags);
+/* The batched block transforms as the coset openings and the recovery launch them (a test primitive, like
+ * kgs_ntt_ex): B = 2^(logtotal - s) transforms of size m = 2^s over the consecutive blocks of one array of
+ * 2^logtotal elements, in place on the device. in_mont and out_mont hold 2^logtotal elements; block b is the
+ * elements b m .. b m + m - 1; rev = the bit reversal of s-bit indices; NTT / INTT = kgs_ntt's forward / inverse
+ * of size m (INTT with its 1/m). For every block b < B and k < m:
+ *   forward (no KGS_NTT_INVERSE): x_j = in[b m + j]          out[b m + k] = NTT(x)_rev(k)   (natural in, bit-reversed out)
+ *   inverse (KGS_NTT_INVERSE):    e_j = in[b m + rev(j)]     out[b m + k] = INTT(e)_k       (bit-reversed in, natural out)
+ *     with KGS_NTT_NO_SCALE                                  out[b m + k] = m INTT(e)_k = sum_j e_j w^(-jk), w = Fr.w[s]
+ *   KGS_NTT_INFLIGHT the pass build of one-lane (in-flight) contexts instead of the default one (same values)
+ * That is kgs_ntt_ex(block, m, s, KGS_NTT_BITREV) and kgs_ntt_ex(block, m, s, KGS_NTT_INVERSE | KGS_NTT_BITREV
+ * [| KGS_NTT_NO_SCALE]) block by block; s == 0 returns the input. The domain tables grow to 2^s only, never to
+ * 2^logtotal, as in the calls that launch these transforms (kgs_kzg_open_cosets_many, kgs_kzg_recover_cosets,
+ * kgs_kzg_recover_cosets_many): the passes read the stage tables by stage, not by transform size.
+ * KGS_E_ARG: logtotal outside 0 .. 28, s outside 0 .. logtotal, a flag bit other than the three above, NULL. */
+int kgs_ntt_blocks(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logtotal, int s, int flags);
 /* [ffjs] G1.multiExpAffine(SRS[0..n), fromMont(scalars)) + toAffine (polynomial.js:1106-1115).
  * The scalars are canonical Montgomery forms (below r; any representative below 2^254 is taken). */
 int kgs_msm(kgs_ctx_t* ctx, const uint8_t* scalars_mont, uint64_t n, uint8_t out_lem[64]);

@@ -138,6 +138,7 @@ def lib():
         L.kgs_fr_batch_inverse.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_uint64]
         L.kgs_ntt.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_int]
         L.kgs_ntt_ex.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_int, ctypes.c_int]
+        L.kgs_ntt_blocks.argtypes = [ctypes.c_void_p, c_u8p, c_u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.kgs_msm.argtypes = [ctypes.c_void_p, c_u8p, ctypes.c_uint64, c_u8p]
         L.kgs_grand_build.argtypes = [ctypes.c_void_p, ctypes.c_int, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p,
                                       ctypes.c_uint64, c_u8p]
@@ -634,6 +635,18 @@ class Context:
             raise ValueError("an inverse transform takes 2^logm elements")
         out = ctypes.create_string_buffer(32 << logm if 0 <= logm <= 28 else 32)
         _check(lib().kgs_ntt_ex(self._h, _buf(data) if in_len else None, in_len, out, logm, flags))
+        return out.raw
+
+    def ntt_blocks(self, data, logtotal, s, flags=0):
+        """kgs_ntt_blocks: the 2^(logtotal - s) transforms of size 2^s over the consecutive blocks of data
+        (2^logtotal elements) as the coset openings and the recovery launch them. Forward: every block natural
+        in, bit-reversed out; NTT_INVERSE: bit-reversed in, natural out, with 1/2^s unless NTT_NO_SCALE;
+        NTT_INFLIGHT: the other pass build. include/kgs.h states the result as a formula."""
+        in_range = 0 <= logtotal <= 28  # else the library refuses before it reads
+        if in_range and len(data) != 32 << logtotal:
+            raise ValueError("the block transforms take 2^logtotal elements")
+        out = ctypes.create_string_buffer(32 << logtotal if in_range else 32)
+        _check(lib().kgs_ntt_blocks(self._h, _buf(data), out, logtotal, s, flags))
         return out.raw
 
     def msm(self, scalars_mont):

@@ -175,6 +175,30 @@ int kgs_ntt_ex(kgs_ctx_t* ctx, const uint8_t* in_mont, uint64_t in_len, uint8_t*
   API_END
 }
 
+// The batched block transforms as the coset openings and the recovery launch them (kgs.h): in place on one
+// device buffer, the domain tables no larger than one block needs.
+int kgs_ntt_blocks(kgs_ctx_t* ctx, const uint8_t* in_mont, uint8_t* out_mont, int logtotal, int s, int flags) {
+  API_BEGIN
+  Prim p(ctx);
+  if (logtotal < 0 || logtotal > 28) throw KgsError(KGS_E_ARG, "bad logtotal");
+  if (s < 0 || s > logtotal) throw KgsError(KGS_E_ARG, "s must be in 0 .. logtotal");
+  if (flags & ~(KGS_NTT_INVERSE | KGS_NTT_NO_SCALE | KGS_NTT_INFLIGHT)) throw KgsError(KGS_E_ARG, "unknown NTT flag");
+  if (!in_mont || !out_mont) throw KgsError(KGS_E_ARG, "NULL argument");
+  if (s > ctx->logM) ensure_domain(*ctx, s);  // never logtotal: the stage tables are indexed by stage
+  const size_t bytes = (size_t)32 << logtotal;
+  uint32_t* a = p.up("prim_a", in_mont, bytes);
+  {
+    NttMode ntt_mode((flags & KGS_NTT_INFLIGHT) != 0);
+    if (flags & KGS_NTT_INVERSE)
+      ntt_dit_blocks(ctx->st, a, logtotal, s, ctx->tw_inv, (flags & KGS_NTT_NO_SCALE) ? nullptr : ctx->invm + 8 * s);
+    else
+      ntt_dif_blocks(ctx->st, a, logtotal, s, ctx->tw_fwd);
+    check_launch();
+  }
+  p.finish(out_mont, a, bytes);
+  API_END
+}
+
 int kgs_grand_build(kgs_ctx_t* ctx, int kind, const uint8_t* f_mont, const uint8_t* t_mont, const uint8_t* sel_f,
                     const uint8_t* sel_t, const uint8_t gamma_mont[32], uint64_t n, uint8_t* out_mont) {
   API_BEGIN

@@ -1,9 +1,11 @@
 """References of kgs_ntt_ex (include/kgs.h), written from the header's formulas over the plain transform:
 with Python integers and oracle/poly.py up to 2^12 (`ref_py`), with the C restatement above (`ref_c`:
-oracle.c's ntt and scale_powers). tests/test_oracle_c.py pins the two to each other.
+oracle.c's ntt and scale_powers). tests/test_oracle_c.py pins the two to each other. `ref_blocks` is the
+reference of kgs_ntt_blocks: the same references block by block.
 
 Flags are the header's values, read from it together with the coset generator.
 """
+import functools
 import os
 import re
 
@@ -25,6 +27,7 @@ NO_SCALE, INPLACE, INFLIGHT = _define("KGS_NTT_NO_SCALE"), _define("KGS_NTT_INPL
 PY_MAX_LOGM = 12
 
 
+@functools.lru_cache(None)
 def rev(k, logm):
     return int(format(k, "0%db" % logm)[::-1], 2) if logm else 0
 
@@ -95,6 +98,19 @@ def ref(data, logm, flags):
     if logm <= PY_MAX_LOGM:
         return common.mont_bytes(ref_py(unmont(data), logm, flags))
     return ref_c(data, logm, flags)
+
+
+def ref_blocks(data, logtotal, s, flags):
+    """The expected bytes of Context.ntt_blocks(data, logtotal, s, flags) (kgs_ntt_blocks, include/kgs.h): the
+    2^(logtotal - s) consecutive blocks of 2^s elements, each through `ref` on its own: forward natural in,
+    bit-reversed out; inverse bit-reversed in, natural out, with 1/2^s unless NO_SCALE."""
+    assert 0 <= s <= logtotal and len(data) == 32 << logtotal and not flags & ~(INVERSE | NO_SCALE | INFLIGHT)
+    f = BITREV | (flags & INVERSE) | (flags & NO_SCALE if flags & INVERSE else 0)
+    if s <= PY_MAX_LOGM:  # `ref` of every block, the bytes converted once for all of them
+        vals, m = unmont(data), 1 << s
+        return common.mont_bytes([y for at in range(0, len(vals), m) for y in ref_py(vals[at:at + m], s, f)])
+    size = 32 << s
+    return b"".join(ref_c(data[at:at + size], s, f) for at in range(0, len(data), size))
 
 
 def random_elements(seed, count):

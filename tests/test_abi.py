@@ -30,7 +30,7 @@ def lib():
 def test_header_declares_api():
     syms = declared_symbols()
     for s in ("kgs_ctx_create", "kgs_srs_load_ptau", "kgs_prove", "kgs_prove_device", "kgs_msm", "kgs_ntt",
-              "kgs_ntt_ex", "kgs_grand_build", "kgs_poly_eval", "kgs_poly_div_x_sub", "kgs_keccak256",
+              "kgs_ntt_ex", "kgs_ntt_blocks", "kgs_grand_build", "kgs_poly_eval", "kgs_poly_div_x_sub", "kgs_keccak256",
               "kgs_quotient_ex", "kgs_divcheck", "kgs_lincomb"):
         assert s in syms
 

@@ -159,6 +159,31 @@ def test_mapping_seams_of_the_batched_stage(ctx, polys):
     assert ctx.idle()
 
 
+@pytest.mark.parametrize("nbits,lbits", [(3, 0), (4, 1), (5, 2)])
+def test_the_four_stage_pass_of_the_fr_side(ctx, nbits, lbits):
+    """m = 8 and 130 polynomials: the Fr side is l * 130 blocks of 2m = 16 over an array of 2^12, 2^13, 2^14
+    elements, one LDS pass of four stages (two register rounds of two), which no whole transform and no shape above
+    launches. Every proof against the closed form on the CPU."""
+    polys = 130
+    ps = polys_of(nbits, polys, 6)
+    proofs = ctx.kzg_open_cosets_many([Z.mont(p) for p in ps], nbits, lbits)
+    for b, p in enumerate(ps):
+        assert proofs[b] == N.points(C.closed_scalars(p, nbits, lbits)), (nbits, lbits, b)
+    assert ctx.idle()
+
+
+def test_the_four_stage_pass_of_the_evaluations(ctx):
+    """(4, 1) with the evaluations: 130 blocks of n = 16 over an array of 2^12 as well; against the single call"""
+    nbits, lbits, polys = 4, 1, 130
+    ps = polys_of(nbits, polys, 6)
+    proofs, ev = ctx.kzg_open_cosets_many([Z.mont(p) for p in ps], nbits, lbits, evals=True)
+    assert len(proofs) == len(ev) == polys
+    for b, p in enumerate(ps):
+        assert (proofs[b], ev[b]) == single(ctx, p, nbits, lbits), b
+        assert ev[b] == Z.mont(Z.evals(p, nbits)), b  # and the integer transform
+    assert ctx.idle()
+
+
 # ------------------------------------------------------------------ contents
 def test_zero_equal_and_opposite_polynomials(ctx):
     """a zero polynomial among others (its points are the identity through every stage), the same polynomial

@@ -150,6 +150,15 @@ def test_block_transform_seams(plain, nbits, polys):
     run_seam(plain, nbits, nbits - 3, polys, 13500 + 10 * nbits, shifts=(1,))
 
 
+@pytest.mark.parametrize("nbits,lbits", [(4, 0), (4, 1)])
+def test_the_four_stage_pass(plain, nbits, lbits):
+    """130 polynomials, P = 256: blocks of 2^4 over an array of 2^12 take the one LDS pass of four stages (two register
+    rounds of two), which no whole transform and no shape above launches. (4, 0): on the m side and the n side;
+    (4, 1): on the n side, beside m = 8 by the radix pass"""
+    assert 4 + 8 >= TILE_LOG
+    run_seam(plain, nbits, lbits, 130, 15000 + 10 * lbits, evals=True)
+
+
 @pytest.mark.parametrize("polys", [7, 8, 9, 31, 32, 33])
 def test_padding_to_a_power_of_two(plain, polys):
     run_seam(plain, 6, 3, polys, 14000 + polys, evals=True)
